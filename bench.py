@@ -15,8 +15,12 @@ configs #2 and #4 combined).
 Usage (driver contract):
   python bench.py --gpus N --steps K --warmup W
   # N>1 is launched via torch.distributed.run; RANK/WORLD_SIZE read from env
+  python bench.py ... --dump-outputs DIR   # also write the last cycle's results as .npy
+  python bench.py ... --full               # also run secondary measurements (none yet)
 
-Rank 0 prints ONE JSON line with the aggregate metric.
+A plain run does only what the headline needs: start the daemon, warm up,
+time the K cycles, print. Anything else the benchmark grows belongs behind
+--full. Rank 0 prints ONE JSON line with the aggregate metric.
 """
 from __future__ import annotations
 
@@ -40,6 +44,19 @@ def parse_args():
         default="proc",
         choices=["proc", "mock", "docker"],
         help="container runtime driver (docker needs a live dockerd socket)",
+    )
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write what the last timed cycle returned "
+        "(response codes, versioned container names) as DIR/<name>.npy",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run every secondary measurement or check besides the headline "
+        "figure (none exist yet: a plain run already does only what the headline needs)",
     )
     return p.parse_args()
 
@@ -140,12 +157,13 @@ class DaemonThread:
                 self._engine_proc.kill()
 
 
-def one_cycle(client, name: str, patch_to: int) -> float:
+def one_cycle(client, name: str, patch_to: int, responses: list | None = None) -> float:
     """One timed cycle: create(1 GPU)->running, patch gpuCount 1->patch_to
     (rolling replace with GPU re-schedule), delete. Returns latency in ms.
-    Raises on any non-200 code."""
+    Raises on any non-200 code. When ``responses`` is a list, the three
+    response bodies (create, patch, delete) are appended to it."""
     t0 = time.perf_counter()
-    r = client.post(
+    created = r = client.post(
         "/api/v1/replicaSet",
         json={
             "imageName": "synthetic:bench",
@@ -156,13 +174,47 @@ def one_cycle(client, name: str, patch_to: int) -> float:
         },
     ).json()
     assert r["code"] == 200, f"run failed: {r}"
-    r = client.patch(
+    patched = r = client.patch(
         f"/api/v1/replicaSet/{name}", json={"gpuPatch": {"gpuCount": patch_to}}
     ).json()
     assert r["code"] == 200, f"patch failed: {r}"
     r = client.delete(f"/api/v1/replicaSet/{name}").json()
     assert r["code"] == 200, f"delete failed: {r}"
-    return (time.perf_counter() - t0) * 1000.0
+    latency_ms = (time.perf_counter() - t0) * 1000.0
+    if responses is not None:
+        responses.extend([created, patched, r])
+    return latency_ms
+
+
+NAME_WIDTH = 64  # bytes per container name in names_utf8.npy (zero padded)
+
+
+def dump_outputs(out_dir: str, responses: list) -> None:
+    """Write what the last timed cycle returned to its caller as .npy arrays.
+
+    The cycle's results are three JSON bodies, so the deterministic part of
+    each is encoded numerically (ids and phase timings differ from run to
+    run and are left out):
+
+      codes.npy       float64 [3]     response code of create, patch, delete
+      versions.npy    float64 [2]     version suffix of the container name
+                                      create and patch returned (name-<N>)
+      names_utf8.npy  float32 [2,64]  those two names as UTF-8 byte values
+    """
+    import numpy as np
+
+    create, patch, delete = responses
+    names = [create["data"]["name"], patch["data"]["containerName"]]
+    codes = np.array([create["code"], patch["code"], delete["code"]], dtype=np.float64)
+    versions = np.array([int(n.rsplit("-", 1)[1]) for n in names], dtype=np.float64)
+    names_utf8 = np.zeros((len(names), NAME_WIDTH), dtype=np.float32)
+    for i, n in enumerate(names):
+        raw = n.encode("utf-8")[:NAME_WIDTH]
+        names_utf8[i, : len(raw)] = list(raw)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "codes.npy"), codes)
+    np.save(os.path.join(out_dir, "versions.npy"), versions)
+    np.save(os.path.join(out_dir, "names_utf8.npy"), names_utf8)
 
 
 def main():
@@ -234,7 +286,11 @@ def main():
 
     barrier_sync()
     t_start = time.perf_counter()
-    latencies = [one_cycle(client, name, patch_to) for _ in range(args.steps)]
+    last: list = []  # response bodies of the last timed cycle
+    latencies = [
+        one_cycle(client, name, patch_to, last if i == args.steps - 1 else None)
+        for i in range(args.steps)
+    ]
     barrier_sync()
     elapsed_s = time.perf_counter() - t_start
 
@@ -249,6 +305,8 @@ def main():
         all_elapsed = [elapsed_s]
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
         merged = sorted(x for l in all_lat for x in l)
         p50 = statistics.median(merged)
         max_elapsed = max(all_elapsed)

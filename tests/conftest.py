@@ -22,6 +22,24 @@ def run():
     return _run
 
 
+@pytest.fixture
+def sock_dir():
+    """A short-lived directory for unix sockets. sockaddr_un.sun_path holds
+    at most 107 bytes, and pytest's tmp_path (base temp + user + test name)
+    can exceed that, so sockets get a directory with a short path instead."""
+    import shutil
+    import tempfile
+
+    base = tempfile.gettempdir()
+    if len(base) > 60:
+        base = "/tmp"
+    d = tempfile.mkdtemp(prefix="gda-", dir=base)
+    try:
+        yield d
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 def require_gpu():
     try:
         import torch

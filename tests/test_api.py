@@ -176,7 +176,11 @@ def test_gpu_validate_endpoint_graceful_without_gpu(client):
     # clean 500-coded error — never a crash
     assert body["code"] in (200, 500)
     if body["code"] == 200:
-        assert body["data"]["gpus"] == []
+        # where a GPU is visible after all, the report covers each device
+        import torch
+
+        n = torch.cuda.device_count() if torch.cuda.is_available() else 0
+        assert len(body["data"]["gpus"]) == n
 
 
 def test_apikey_auth(tmp_path):

@@ -12,6 +12,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_gloo():
     env = dict(os.environ)
     env.pop("ROCR_VISIBLE_DEVICES", None)
+    # this is the CPU/gloo topology test: hide any GPU from the ranks, or on
+    # a 1-GPU machine both ranks pick nccl and collide on the same device
+    env["HIP_VISIBLE_DEVICES"] = ""
+    env["CUDA_VISIBLE_DEVICES"] = ""
     out = subprocess.run(
         [
             sys.executable,

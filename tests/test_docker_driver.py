@@ -3,6 +3,7 @@ verifies request construction — ROCm device injection, no NVIDIA runtime,
 exec stream demux — without a real dockerd."""
 import asyncio
 import json
+import os
 import struct
 
 import pytest
@@ -85,12 +86,12 @@ def _resolver(uuid):
     )
 
 
-def test_create_cdi_mode(tmp_path, run):
+def test_create_cdi_mode(sock_dir, run):
     async def main():
         fake = FakeDockerd()
         runner = web.AppRunner(fake.app())
         await runner.setup()
-        sock = str(tmp_path / "docker.sock")
+        sock = os.path.join(sock_dir, "docker.sock")
         await web.UnixSite(runner, sock).start()
         rt = DockerRuntime(socket_path=sock, gpu_resolver=_resolver, use_cdi=True)
         spec = ContainerSpec()
@@ -110,12 +111,12 @@ def test_create_cdi_mode(tmp_path, run):
     run(main())
 
 
-def test_create_injects_rocm_devices(tmp_path, run):
+def test_create_injects_rocm_devices(sock_dir, run):
     async def main():
         fake = FakeDockerd()
         runner = web.AppRunner(fake.app())
         await runner.setup()
-        sock = str(tmp_path / "docker.sock")
+        sock = os.path.join(sock_dir, "docker.sock")
         site = web.UnixSite(runner, sock)
         await site.start()
 

@@ -43,8 +43,8 @@ def _wait_for(pred, timeout=20.0, what="condition"):
 
 
 @pytest.fixture
-def dockerd_sim(tmp_path):
-    sock = str(tmp_path / "dockerd.sock")
+def dockerd_sim(tmp_path, sock_dir):
+    sock = os.path.join(sock_dir, "dockerd.sock")
     proc = subprocess.Popen(
         [sys.executable, "-m", "gpu_docker_api_amd.testing.dockerd_sim",
          "--socket", sock, "--data", str(tmp_path / "engine")],
@@ -438,7 +438,7 @@ def test_docker_logs_over_socket(dockerd_sim, tmp_path, run):
     run(main())
 
 
-def test_engine_restart_preserves_containers(tmp_path, run):
+def test_engine_restart_preserves_containers(tmp_path, sock_dir, run):
     """Engine-side durability over the wire: kill the dockerd-sim process
     and start a new one on the same data dir — the driver must still see
     the container (adopted live by the new engine), like a real dockerd
@@ -446,7 +446,7 @@ def test_engine_restart_preserves_containers(tmp_path, run):
     from gpu_docker_api_amd.models.etcd import ContainerSpec
     from gpu_docker_api_amd.runtime.docker import DockerRuntime
 
-    sock1 = str(tmp_path / "d1.sock")
+    sock1 = os.path.join(sock_dir, "d1.sock")
     data = str(tmp_path / "engine")
 
     def spawn(sock):
@@ -480,7 +480,7 @@ def test_engine_restart_preserves_containers(tmp_path, run):
         proc1.kill()
         proc1.wait(timeout=10)
 
-        sock2 = str(tmp_path / "d2.sock")
+        sock2 = os.path.join(sock_dir, "d2.sock")
         proc2 = spawn(sock2)
         _wait_for(lambda: os.path.exists(sock2), what="restarted engine socket")
 

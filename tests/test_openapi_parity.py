@@ -1,16 +1,19 @@
 """Route/body parity against the reference OpenAPI + Go structs is proven by
-scripts/openapi_parity.py; this keeps it true in CI (VERDICT r1 missing #4)."""
+scripts/openapi_parity.py; this keeps it true in CI (VERDICT r1 missing #4).
+
+The reference's published surface (every operation and the request-body
+field names its OpenAPI document lists) is stored under tests/golden/ in the
+minimal OpenAPI shape the parity script reads, so the test needs nothing
+outside the repository."""
 import os
 import sys
 
-import pytest
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
-
-REF = "/root/reference/api/gpu-docker-api-en.openapi.json"
+REF = os.path.join(ROOT, "tests", "golden", "reference_api_surface.json")
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference spec not present")
 def test_parity_clean():
     import openapi_parity
 
