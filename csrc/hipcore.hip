@@ -407,6 +407,38 @@ std::vector<std::vector<double>> p2p_matrix(int mib, int iters) {
 // Torch bindings
 // ---------------------------------------------------------------------------
 
+// The GEMM kernels stage with 16-byte global_load_lds (and the dwordx4
+// epilogue stores 16 bytes), the copy kernels reinterpret as float4: a
+// contiguous view with a storage offset that is not a multiple of 16 bytes
+// must be rejected before any launch.
+void check_aligned16(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0, name,
+              ": data pointer must be 16-byte aligned");
+}
+
+// Resolve the optional `out` argument of the GEMM bindings: allocate when
+// absent, otherwise require an fp32 contiguous [M, N] tensor on A's device.
+torch::Tensor resolve_out(const c10::optional<torch::Tensor>& out, int64_t M,
+                          int64_t N, const torch::Tensor& A) {
+  if (!out.has_value())
+    return torch::empty({M, N}, A.options().dtype(torch::kFloat32));
+  const torch::Tensor& C = *out;
+  TORCH_CHECK(C.is_cuda() && C.device() == A.device(),
+              "out: must be on the same device as A");
+  TORCH_CHECK(C.scalar_type() == torch::kFloat32, "out: must be float32");
+  TORCH_CHECK(C.dim() == 2 && C.size(0) == M && C.size(1) == N,
+              "out: must have shape [M, N] = [", M, ", ", N, "]");
+  TORCH_CHECK(C.is_contiguous(), "out: must be contiguous");
+  return C;
+}
+
+void check_gemm_operands(const torch::Tensor& A, const torch::Tensor& B,
+                         const char* bname) {
+  TORCH_CHECK(A.is_cuda() && B.is_cuda(), "GPU tensors required");
+  TORCH_CHECK(A.device() == B.device(), "operands must share a device");
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2, "A and ", bname, " must be 2-D");
+}
+
 void copy_f32(torch::Tensor dst, torch::Tensor src) {
   TORCH_CHECK(src.is_cuda() && dst.is_cuda(), "tensors must be on GPU");
   TORCH_CHECK(src.scalar_type() == torch::kFloat32 &&
@@ -414,22 +446,29 @@ void copy_f32(torch::Tensor dst, torch::Tensor src) {
               "f32 only");
   TORCH_CHECK(src.is_contiguous() && dst.is_contiguous(), "contiguous only");
   TORCH_CHECK(src.numel() == dst.numel(), "size mismatch");
+  check_aligned16(src, "src");
+  check_aligned16(dst, "dst");
   auto stream = at::hip::getCurrentHIPStream();
   launch_copy_f32(src.data_ptr<float>(), dst.data_ptr<float>(), src.numel(),
                   stream.stream());
 }
 
-torch::Tensor mfma_f32_matmul(torch::Tensor A, torch::Tensor B) {
-  TORCH_CHECK(A.is_cuda() && B.is_cuda(), "GPU tensors required");
+torch::Tensor mfma_f32_matmul(torch::Tensor A, torch::Tensor B,
+                              c10::optional<torch::Tensor> out) {
+  check_gemm_operands(A, B, "B");
   TORCH_CHECK(A.scalar_type() == torch::kFloat32 &&
               B.scalar_type() == torch::kFloat32, "f32 only");
   A = A.contiguous();
   B = B.contiguous();
   int M = A.size(0), K = A.size(1), N = B.size(1);
   TORCH_CHECK(B.size(0) == K, "shape mismatch");
-  TORCH_CHECK(M % 16 == 0 && N % 16 == 0 && K % 4 == 0,
-              "M,N multiples of 16; K multiple of 4");
-  auto C = torch::empty({M, N}, A.options());
+  TORCH_CHECK(M >= 16 && N >= 16 && K >= 4 && M % 16 == 0 && N % 16 == 0 &&
+                  K % 4 == 0,
+              "M,N multiples of 16; K multiple of 4, >= 4");
+  check_aligned16(A, "A");
+  check_aligned16(B, "B");
+  auto C = resolve_out(out, M, N, A);
+  check_aligned16(C, "out");
   int waves = (M / 16) * (N / 16);
   constexpr int kWavesPerBlock = 4;  // 256 threads
   int grid = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -441,17 +480,22 @@ torch::Tensor mfma_f32_matmul(torch::Tensor A, torch::Tensor B) {
   return C;
 }
 
-torch::Tensor mfma_bf16_matmul(torch::Tensor A, torch::Tensor B) {
-  TORCH_CHECK(A.is_cuda() && B.is_cuda(), "GPU tensors required");
+torch::Tensor mfma_bf16_matmul(torch::Tensor A, torch::Tensor B,
+                               c10::optional<torch::Tensor> out) {
+  check_gemm_operands(A, B, "B");
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 &&
               B.scalar_type() == torch::kBFloat16, "bf16 only");
   A = A.contiguous();
   B = B.contiguous();
   int M = A.size(0), K = A.size(1), N = B.size(1);
   TORCH_CHECK(B.size(0) == K, "shape mismatch");
-  TORCH_CHECK(M % 16 == 0 && N % 16 == 0 && K % 32 == 0,
-              "M,N multiples of 16; K multiple of 32");
-  auto C = torch::empty({M, N}, A.options().dtype(torch::kFloat32));
+  TORCH_CHECK(M >= 16 && N >= 16 && K >= 32 && M % 16 == 0 && N % 16 == 0 &&
+                  K % 32 == 0,
+              "M,N multiples of 16; K multiple of 32, >= 32");
+  check_aligned16(A, "A");
+  check_aligned16(B, "B");
+  auto C = resolve_out(out, M, N, A);
+  check_aligned16(C, "out");
   int waves = (M / 16) * (N / 16);
   constexpr int kWavesPerBlock = 4;
   int grid = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -464,37 +508,61 @@ torch::Tensor mfma_bf16_matmul(torch::Tensor A, torch::Tensor B) {
   return C;
 }
 
-torch::Tensor gemm_bf16_bt(torch::Tensor A, torch::Tensor Bt) {
-  TORCH_CHECK(A.is_cuda() && Bt.is_cuda(), "GPU tensors required");
+// BK of the 128^2 kernel: 32 or 64; 0 picks the widest K-step that divides K
+// (the binding's default). Validated once, before any launch.
+int resolve_bf16_bk(int bk, int K) {
+  if (bk == 0) bk = (K % 64 == 0) ? 64 : 32;
+  TORCH_CHECK(bk == 32 || bk == 64, "bk must be 0 (auto), 32 or 64");
+  TORCH_CHECK(K % bk == 0, "K must be a multiple of bk");
+  return bk;
+}
+
+// The one BK -> instantiation table of the 128^2 kernel, shared by the
+// tensor binding and gemm_bf16_tflops. bk comes from resolve_bf16_bk.
+void launch_bf16_tile(int bk, int swizzle, dim3 grid, hipStream_t s,
+                      const __hip_bfloat16* A, const __hip_bfloat16* Bt,
+                      float* C, int M, int N, int K) {
+  if (bk == 32) {
+    hipLaunchKernelGGL(gemm_bf16::gemm_bf16_tile_kernel<32>, grid, dim3(256),
+                       0, s, A, Bt, C, M, N, K, swizzle);
+  } else {
+    hipLaunchKernelGGL(gemm_bf16::gemm_bf16_tile_kernel<64>, grid, dim3(256),
+                       0, s, A, Bt, C, M, N, K, swizzle);
+  }
+}
+
+torch::Tensor gemm_bf16_bt(torch::Tensor A, torch::Tensor Bt, int swizzle,
+                           int bk, c10::optional<torch::Tensor> out) {
+  check_gemm_operands(A, Bt, "Bt");
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 &&
               Bt.scalar_type() == torch::kBFloat16, "bf16 only");
   A = A.contiguous();
   Bt = Bt.contiguous();
   int M = A.size(0), K = A.size(1), N = Bt.size(0);
   TORCH_CHECK(Bt.size(1) == K, "Bt must be [N][K]");
-  TORCH_CHECK(M % 128 == 0 && N % 128 == 0 && K % 32 == 0,
-              "M,N multiples of 128; K multiple of 32");
-  auto C = torch::empty({M, N}, A.options().dtype(torch::kFloat32));
+  TORCH_CHECK(M >= 128 && N >= 128 && K >= 32 && M % 128 == 0 &&
+                  N % 128 == 0 && K % 32 == 0,
+              "M,N multiples of 128; K multiple of 32, >= 32");
+  TORCH_CHECK(swizzle == 0 || swizzle == 1, "swizzle must be 0 or 1");
+  bk = resolve_bf16_bk(bk, K);
+  check_aligned16(A, "A");
+  check_aligned16(Bt, "Bt");
+  auto C = resolve_out(out, M, N, A);
+  check_aligned16(C, "out");
   int grid = (M / 128) * (N / 128);
   auto stream = at::hip::getCurrentHIPStream();
-  if (K % 64 == 0) {
-    hipLaunchKernelGGL(gemm_bf16::gemm_bf16_tile_kernel<64>, dim3(grid),
-                       dim3(256), 0, stream.stream(),
-                       reinterpret_cast<const __hip_bfloat16*>(A.data_ptr()),
-                       reinterpret_cast<const __hip_bfloat16*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K, /*swizzle=*/0);
-  } else {
-    hipLaunchKernelGGL(gemm_bf16::gemm_bf16_tile_kernel<32>, dim3(grid),
-                       dim3(256), 0, stream.stream(),
-                       reinterpret_cast<const __hip_bfloat16*>(A.data_ptr()),
-                       reinterpret_cast<const __hip_bfloat16*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K, /*swizzle=*/0);
-  }
+  launch_bf16_tile(bk, swizzle, dim3(grid), stream.stream(),
+                   reinterpret_cast<const __hip_bfloat16*>(A.data_ptr()),
+                   reinterpret_cast<const __hip_bfloat16*>(Bt.data_ptr()),
+                   C.data_ptr<float>(), M, N, K);
   return C;
 }
 
 // Dense bf16 throughput on one device (the health-check burn-in number).
 double gemm_bf16_tflops(int device, int size, int iters, int swizzle, int bk) {
+  if (bk != 32) bk = 64;  // historical: anything but 32 times the BK=64 kernel
+  TORCH_CHECK(size >= 128 && size % 128 == 0, "size must be a multiple of 128");
+  bk = resolve_bf16_bk(bk, size);
   HIP_CHECK(hipSetDevice(device));
   mfma_warmup(device, 20000);
   size_t n = (size_t)size * size;
@@ -510,13 +578,7 @@ double gemm_bf16_tflops(int device, int size, int iters, int swizzle, int bk) {
   double ms = time_kernel_ms(
       device,
       [&](hipStream_t s) {
-        if (bk == 32) {
-          hipLaunchKernelGGL(gemm_bf16::gemm_bf16_tile_kernel<32>, dim3(grid),
-                             dim3(256), 0, s, A, Bt, C, size, size, size, swizzle);
-        } else {
-          hipLaunchKernelGGL(gemm_bf16::gemm_bf16_tile_kernel<64>, dim3(grid),
-                             dim3(256), 0, s, A, Bt, C, size, size, size, swizzle);
-        }
+        launch_bf16_tile(bk, swizzle, dim3(grid), s, A, Bt, C, size, size, size);
       },
       iters);
   (void)hipFree(A);
@@ -582,24 +644,33 @@ void launch_8ph(int variant, dim3 grid, hipStream_t s,
       hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, 0, 1>), grid,
                          dim3(512), 0, s, A, Bt, C, M, N, K);
       break;
-    default:
+    case 0:
       hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, 0>), grid,
                          dim3(512), 0, s, A, Bt, C, M, N, K);
       break;
+    default:
+      TORCH_CHECK(false, "unknown 8-phase variant ", variant, " (0..12)");
   }
 }
 
-torch::Tensor gemm_bf16_8ph_bt(torch::Tensor A, torch::Tensor Bt, int variant) {
-  TORCH_CHECK(A.is_cuda() && Bt.is_cuda(), "GPU tensors required");
+torch::Tensor gemm_bf16_8ph_bt(torch::Tensor A, torch::Tensor Bt, int variant,
+                               c10::optional<torch::Tensor> out) {
+  check_gemm_operands(A, Bt, "Bt");
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 &&
               Bt.scalar_type() == torch::kBFloat16, "bf16 only");
   A = A.contiguous();
   Bt = Bt.contiguous();
   int M = A.size(0), K = A.size(1), N = Bt.size(0);
   TORCH_CHECK(Bt.size(1) == K, "Bt must be [N][K]");
-  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && K >= 192,
+  TORCH_CHECK(M >= 256 && N >= 256 && M % 256 == 0 && N % 256 == 0 &&
+                  K % 64 == 0 && K >= 192,
               "M,N multiples of 256; K multiple of 64, >= 192");
-  auto C = torch::empty({M, N}, A.options().dtype(torch::kFloat32));
+  TORCH_CHECK(variant >= 0 && variant <= 12, "unknown 8-phase variant ",
+              variant, " (0..12)");
+  check_aligned16(A, "A");
+  check_aligned16(Bt, "Bt");
+  auto C = resolve_out(out, M, N, A);
+  check_aligned16(C, "out");
   int grid = (M / 256) * (N / 256);
   auto stream = at::hip::getCurrentHIPStream();
   launch_8ph(variant, dim3(grid), stream.stream(),
@@ -610,6 +681,9 @@ torch::Tensor gemm_bf16_8ph_bt(torch::Tensor A, torch::Tensor Bt, int variant) {
 }
 
 double gemm_bf16_8ph_tflops(int device, int size, int iters, int variant) {
+  TORCH_CHECK(variant >= 0 && variant <= 12, "unknown 8-phase variant ",
+              variant, " (0..12)");
+  TORCH_CHECK(size >= 256 && size % 256 == 0, "size must be a multiple of 256");
   HIP_CHECK(hipSetDevice(device));
   mfma_warmup(device, 20000);
   size_t n = (size_t)size * size;
@@ -639,6 +713,9 @@ double gemm_bf16_8ph_tflops(int device, int size, int iters, int variant) {
 // process). Returns {variant: [tflops per round]}.
 py::dict gemm_bf16_8ph_ab(int device, int size, int iters, int rounds,
                           std::vector<int> variants) {
+  for (int v : variants)
+    TORCH_CHECK(v >= 0 && v <= 12, "unknown 8-phase variant ", v, " (0..12)");
+  TORCH_CHECK(size >= 256 && size % 256 == 0, "size must be a multiple of 256");
   HIP_CHECK(hipSetDevice(device));
   mfma_warmup(device, 20000);
   size_t n = (size_t)size * size;
@@ -671,8 +748,81 @@ py::dict gemm_bf16_8ph_ab(int device, int size, int iters, int rounds,
   return d;
 }
 
-torch::Tensor gemm_fp8_mx_bt(torch::Tensor A, torch::Tensor Bt, int shape) {
-  TORCH_CHECK(A.is_cuda() && Bt.is_cuda(), "GPU tensors required");
+// The one shape -> instantiation table of the MX fp8 GEMM, shared by the
+// tensor binding and gemm_fp8_mx_tflops so the numerics tests cover exactly
+// the kernels that are timed. Template axes: <FMT, SWZV, EPI, MP23>.
+bool fp8_mx_shape_known(int shape) {
+  return shape == 16 || shape == 17 || shape == 18 || shape == 20 || shape == 32;
+}
+
+void launch_fp8_mx(int shape, dim3 grid, hipStream_t s, const unsigned char* A,
+                   const unsigned char* Bt, float* C, int M, int N, int K) {
+  switch (shape) {
+    case 32:  // 32x32x64 instruction
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_mx32_kernel<0, 0>), grid, dim3(512),
+                         0, s, A, Bt, C, M, N, K);
+      break;
+    case 20:  // merged phases 2+3
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 0, 1>), grid,
+                         dim3(512), 0, s, A, Bt, C, M, N, K);
+      break;
+    case 18:  // + quad-transpose dwordx4 epilogue
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 1, 0>), grid,
+                         dim3(512), 0, s, A, Bt, C, M, N, K);
+      break;
+    case 17:  // legacy row&7-only swizzle (A/B reference)
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 0, 0, 0>), grid,
+                         dim3(512), 0, s, A, Bt, C, M, N, K);
+      break;
+    case 16:  // default: row-bit-3 swizzle (conflict-free 2-chunk reads, +11%)
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 0, 0>), grid,
+                         dim3(512), 0, s, A, Bt, C, M, N, K);
+      break;
+    default:
+      TORCH_CHECK(false, "unknown fp8 MX shape code ", shape,
+                  " (16, 17, 18, 20, 32)");
+  }
+}
+
+// Same for MX fp4. Code 16 (the default) and 19 are the same instantiation.
+bool fp4_mx_shape_known(int shape) {
+  return shape == 16 || shape == 17 || shape == 18 || shape == 19 ||
+         shape == 21 || shape == 32;
+}
+
+void launch_fp4_mx(int shape, dim3 grid, hipStream_t s, const unsigned char* A,
+                   const unsigned char* Bt, float* C, int M, int N, int K) {
+  switch (shape) {
+    case 32:  // 32x32x64 instruction
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_mx32_kernel<4, 0>), grid, dim3(512),
+                         0, s, A, Bt, C, M, N, K);
+      break;
+    case 18:  // + quad-transpose dwordx4 epilogue
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 1, 0>), grid,
+                         dim3(512), 0, s, A, Bt, C, M, N, K);
+      break;
+    case 17:  // 16x16 with the row-bit-3 swizzle
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 1, 0, 0>), grid,
+                         dim3(512), 0, s, A, Bt, C, M, N, K);
+      break;
+    case 21:  // unmerged legacy (A/B reference)
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 0>), grid,
+                         dim3(512), 0, s, A, Bt, C, M, N, K);
+      break;
+    case 16:  // default: merged phases 2+3 (+1-2% measured both orders)
+    case 19:
+      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 1>), grid,
+                         dim3(512), 0, s, A, Bt, C, M, N, K);
+      break;
+    default:
+      TORCH_CHECK(false, "unknown fp4 MX shape code ", shape,
+                  " (16, 17, 18, 19, 21, 32)");
+  }
+}
+
+torch::Tensor gemm_fp8_mx_bt(torch::Tensor A, torch::Tensor Bt, int shape,
+                             c10::optional<torch::Tensor> out) {
+  check_gemm_operands(A, Bt, "Bt");
   TORCH_CHECK(A.scalar_type() == torch::kUInt8 &&
               Bt.scalar_type() == torch::kUInt8,
               "raw e4m3 bytes expected (uint8 view of float8_e4m3fn)");
@@ -680,47 +830,28 @@ torch::Tensor gemm_fp8_mx_bt(torch::Tensor A, torch::Tensor Bt, int shape) {
   Bt = Bt.contiguous();
   int M = A.size(0), K = A.size(1), N = Bt.size(0);
   TORCH_CHECK(Bt.size(1) == K, "Bt must be [N][K]");
-  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0 && K >= 256,
+  TORCH_CHECK(M >= 256 && N >= 256 && M % 256 == 0 && N % 256 == 0 &&
+                  K % 128 == 0 && K >= 256,
               "M,N multiples of 256; K multiple of 128, >= 256");
-  auto C = torch::empty({M, N}, A.options().dtype(torch::kFloat32));
+  TORCH_CHECK(fp8_mx_shape_known(shape), "unknown fp8 MX shape code ", shape,
+              " (16, 17, 18, 20, 32)");
+  check_aligned16(A, "A");
+  check_aligned16(Bt, "Bt");
+  auto C = resolve_out(out, M, N, A);
+  check_aligned16(C, "out");
   int grid = (M / 256) * (N / 256);
   auto stream = at::hip::getCurrentHIPStream();
-  if (shape == 32)
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_mx32_kernel<0, 0>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
-  else if (shape == 20)  // merged phases 2+3
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 0, 1>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
-  else if (shape == 18)  // + quad-transpose dwordx4 epilogue
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 1>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
-  else if (shape == 17)  // legacy row&7-only swizzle (A/B reference)
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 0>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
-  else  // default: row-bit-3 swizzle (conflict-free for the 2-chunk reads, +11%)
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 0, 0>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
+  launch_fp8_mx(shape, dim3(grid), stream.stream(),
+                reinterpret_cast<const unsigned char*>(A.data_ptr()),
+                reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
+                C.data_ptr<float>(), M, N, K);
   return C;
 }
 
-torch::Tensor gemm_fp4_mx_bt(torch::Tensor A, torch::Tensor Bt, int K, int shape) {
+torch::Tensor gemm_fp4_mx_bt(torch::Tensor A, torch::Tensor Bt, int K, int shape,
+                             c10::optional<torch::Tensor> out) {
   // A [M][K/2], Bt [N][K/2]: e2m1 nibble-packed (low nibble = even k)
-  TORCH_CHECK(A.is_cuda() && Bt.is_cuda(), "GPU tensors required");
+  check_gemm_operands(A, Bt, "Bt");
   TORCH_CHECK(A.scalar_type() == torch::kUInt8 &&
               Bt.scalar_type() == torch::kUInt8, "packed e2m1 bytes expected");
   A = A.contiguous();
@@ -728,51 +859,28 @@ torch::Tensor gemm_fp4_mx_bt(torch::Tensor A, torch::Tensor Bt, int K, int shape
   int M = A.size(0), N = Bt.size(0);
   TORCH_CHECK((long)A.size(1) * 2 == K && (long)Bt.size(1) * 2 == K,
               "K must equal 2 x packed byte columns");
-  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 256 == 0 && K >= 512,
+  TORCH_CHECK(M >= 256 && N >= 256 && M % 256 == 0 && N % 256 == 0 &&
+                  K % 256 == 0 && K >= 512,
               "M,N multiples of 256; K multiple of 256, >= 512");
-  auto C = torch::empty({M, N}, A.options().dtype(torch::kFloat32));
+  TORCH_CHECK(fp4_mx_shape_known(shape), "unknown fp4 MX shape code ", shape,
+              " (16, 17, 18, 19, 21, 32)");
+  check_aligned16(A, "A");
+  check_aligned16(Bt, "Bt");
+  auto C = resolve_out(out, M, N, A);
+  check_aligned16(C, "out");
   int grid = (M / 256) * (N / 256);
   auto stream = at::hip::getCurrentHIPStream();
-  if (shape == 32)
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_mx32_kernel<4, 0>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
-  else if (shape == 19)  // merged phases 2+3
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 1>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
-  else if (shape == 18)  // + quad-transpose dwordx4 epilogue
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 1>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
-  else if (shape == 17)  // 16x16 with the row-bit-3 swizzle
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 1>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
-  else if (shape == 21)  // unmerged legacy (A/B reference)
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 0>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
-  else  // default: merged phases 2+3 (+1-2% measured both orders)
-    hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 1>), dim3(grid), dim3(512),
-                       0, stream.stream(),
-                       reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                       reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                       C.data_ptr<float>(), M, N, K);
+  launch_fp4_mx(shape, dim3(grid), stream.stream(),
+                reinterpret_cast<const unsigned char*>(A.data_ptr()),
+                reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
+                C.data_ptr<float>(), M, N, K);
   return C;
 }
 
 double gemm_fp8_mx_tflops(int device, int size, int iters, int shape) {
+  TORCH_CHECK(fp8_mx_shape_known(shape), "unknown fp8 MX shape code ", shape,
+              " (16, 17, 18, 20, 32)");
+  TORCH_CHECK(size >= 256 && size % 256 == 0, "size must be a multiple of 256");
   HIP_CHECK(hipSetDevice(device));
   mfma_warmup(device, 20000);
   size_t n = (size_t)size * size;
@@ -790,21 +898,7 @@ double gemm_fp8_mx_tflops(int device, int size, int iters, int shape) {
   double ms = time_kernel_ms(
       device,
       [&](hipStream_t s) {
-        if (shape == 32)
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_mx32_kernel<0, 0>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
-        else if (shape == 17)  // legacy swizzle (A/B reference)
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 0>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
-        else if (shape == 20)  // merged phases 2+3
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 0, 1>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
-        else if (shape == 18)  // + quad-transpose dwordx4 epilogue
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 1>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
-        else  // default: row-bit-3 swizzle
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
+        launch_fp8_mx(shape, dim3(grid), s, A, Bt, C, size, size, size);
       },
       iters);
   (void)hipFree(A);
@@ -814,6 +908,10 @@ double gemm_fp8_mx_tflops(int device, int size, int iters, int shape) {
 }
 
 double gemm_fp4_mx_tflops(int device, int size, int iters, int shape) {
+  TORCH_CHECK(fp4_mx_shape_known(shape), "unknown fp4 MX shape code ", shape,
+              " (16, 17, 18, 19, 21, 32)");
+  TORCH_CHECK(size >= 512 && size % 256 == 0,
+              "size must be a multiple of 256, >= 512");
   HIP_CHECK(hipSetDevice(device));
   mfma_warmup(device, 20000);
   size_t nb = (size_t)size * size / 2;  // nibble-packed
@@ -831,24 +929,7 @@ double gemm_fp4_mx_tflops(int device, int size, int iters, int shape) {
   double ms = time_kernel_ms(
       device,
       [&](hipStream_t s) {
-        if (shape == 32)
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_mx32_kernel<4, 0>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
-        else if (shape == 17)
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 1>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
-        else if (shape == 19)  // merged phases 2+3
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 1>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
-        else if (shape == 18)  // + quad-transpose dwordx4 epilogue
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 1>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
-        else if (shape == 21)  // unmerged legacy
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 0>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
-        else  // default: merged phases 2+3
-          hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 1>), dim3(grid),
-                             dim3(512), 0, s, A, Bt, C, size, size, size);
+        launch_fp4_mx(shape, dim3(grid), s, A, Bt, C, size, size, size);
       },
       iters);
   (void)hipFree(A);
@@ -888,17 +969,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("device_count", &device_count);
   m.def("device_info", &device_info, py::arg("device"));
   m.def("copy_f32", &copy_f32, py::arg("dst"), py::arg("src"));
-  m.def("mfma_f32_matmul", &mfma_f32_matmul, py::arg("A"), py::arg("B"));
-  m.def("mfma_bf16_matmul", &mfma_bf16_matmul, py::arg("A"), py::arg("B"));
+  m.def("mfma_f32_matmul", &mfma_f32_matmul, py::arg("A"), py::arg("B"),
+        py::arg("out") = py::none());
+  m.def("mfma_bf16_matmul", &mfma_bf16_matmul, py::arg("A"), py::arg("B"),
+        py::arg("out") = py::none());
   m.def("mfma_warmup", &mfma_warmup, py::arg("device") = 0,
         py::arg("spins") = 20000);
-  m.def("gemm_bf16_bt", &gemm_bf16_bt, py::arg("A"), py::arg("Bt"));
+  m.def("gemm_bf16_bt", &gemm_bf16_bt, py::arg("A"), py::arg("Bt"),
+        py::arg("swizzle") = 0, py::arg("bk") = 0, py::arg("out") = py::none());
   m.def("gemm_bf16_8ph", &gemm_bf16_8ph_bt, py::arg("A"), py::arg("Bt"),
-        py::arg("variant") = 0);
+        py::arg("variant") = 0, py::arg("out") = py::none());
   m.def("gemm_fp8_mx", &gemm_fp8_mx_bt, py::arg("A"), py::arg("Bt"),
-        py::arg("shape") = 16);
+        py::arg("shape") = 16, py::arg("out") = py::none());
   m.def("gemm_fp4_mx", &gemm_fp4_mx_bt, py::arg("A"), py::arg("Bt"), py::arg("K"),
-        py::arg("shape") = 16);
+        py::arg("shape") = 16, py::arg("out") = py::none());
   m.def("gemm_fp4_mx_tflops", &gemm_fp4_mx_tflops, py::arg("device") = 0,
         py::arg("size") = 4096, py::arg("iters") = 10, py::arg("shape") = 16,
         py::call_guard<py::gil_scoped_release>());

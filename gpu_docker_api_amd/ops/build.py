@@ -40,6 +40,7 @@ def build_hipcore(force: bool = False) -> str:
     includes = [
         os.path.join(CSRC, "gemm_bf16.hip"),
         os.path.join(CSRC, "gemm_bf16_8phase.hip"),
+        os.path.join(CSRC, "gemm_fp8_mx.hip"),
     ]
     out = os.path.join(OPS, "_hipcore.so")
     if not force and _newer(out, src, *[p for p in includes if os.path.exists(p)]):

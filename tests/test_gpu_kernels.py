@@ -1,0 +1,576 @@
+"""Exact numerics tests for every compiled GEMM variant, shape edge and copy
+path (hardware-gated: `pytest -m gpu` on a real MI355X).
+
+Protocol for every GEMM call: `out` is the first M*N floats of a larger
+NaN-filled buffer with a 4096-float guard behind it; after the call the
+guard must be untouched, the comparator must pass and no NaN may remain.
+Each case is called three times with `out` re-poisoned before every call —
+a kernel that skips a store, or a race that only shows on some runs, cannot
+hide behind a recycled buffer that already held the right answer.
+
+With the exact operand sets (tests/kernel_refs.py) every product and every
+partial sum is exactly representable in fp32, so the result must equal the
+float64 reference bit for bit whatever the summation order; real-valued and
+full-range operands are judged by the derived K*2^-23*(|A|@|B|^T) bound.
+"""
+import functools
+
+import pytest
+import torch
+
+import kernel_refs as kr
+from conftest import require_gpu
+
+pytestmark = pytest.mark.gpu
+
+REPS = 3  # race screen: every case runs three times, re-poisoned each time
+
+
+@pytest.fixture(scope="module")
+def ext():
+    require_gpu()
+    from gpu_docker_api_amd.ops import hipcore
+
+    return hipcore.load_ext()
+
+
+# ---------------------------------------------------------------------------
+# operands + float64 references, computed once per (kind, shape)
+# ---------------------------------------------------------------------------
+
+_GEN = {
+    "bf16": kr.exact_bf16,
+    "f32": kr.exact_f32,
+    "e4m3": kr.exact_e4m3,
+    "e2m1": kr.all_e2m1,
+    "bf16_real": kr.real_bf16,
+    "f32_real": kr.real_f32,
+    "e4m3_full": kr.full_range_e4m3,
+}
+
+
+@functools.lru_cache(maxsize=None)
+def problem(kind, M, N, K):
+    """A [M][K] and Bt [N][K] from different seeds (so a transposed write
+    shows even where M == N), their device copies and the float64 reference."""
+    if kind in kr.EXACT_SETS:
+        kr.require_exact(kind, K)
+    gen = _GEN[kind]
+    a_raw, a64 = gen(M, K, 1000 + M + K)
+    b_raw, b64 = gen(N, K, 2000 + N + K)
+    return {
+        "A": a_raw.cuda(), "Bt": b_raw.cuda(), "a64": a64, "b64": b64,
+        "ref": kr.reference(a64, b64), "M": M, "N": N, "K": K,
+    }
+
+
+def run_protocol(call, p, compare, label):
+    """`call(out)` runs the kernel into `out`; see the module docstring."""
+    M, N = p["M"], p["N"]
+    buf = kr.PoisonedOut(M * N, "cuda", shape=(M, N))
+    worst = 0.0
+    for rep in range(REPS):
+        buf.poison()
+        ret = call(buf.out)
+        torch.cuda.synchronize()
+        what = f"{label} run {rep}"
+        assert ret.data_ptr() == buf.out.data_ptr(), f"{what}: out not returned"
+        assert buf.guard_intact(), f"{what}: guard behind out was overwritten"
+        try:
+            r = compare(buf.out)
+        except kr.KernelMismatch as e:
+            raise AssertionError(f"{what}: {e}") from None
+        worst = max(worst, r or 0.0)
+        buf.check(what)
+    return worst
+
+
+def exact(p):
+    return lambda C: kr.assert_exact(C, p["ref"])
+
+
+def bounded(p):
+    return lambda C: kr.assert_within_sum_bound(
+        C, p["ref"], p["a64"].abs(), p["b64"].abs(), p["K"])
+
+
+def report(kernel, worst):
+    # the figures quoted in docs/testing.md ("worst observed err/bound")
+    print(f"ERR/BOUND {kernel}: {worst:.4f}")
+    assert worst <= 1.0
+
+
+# ---------------------------------------------------------------------------
+# bf16 8-phase: all 13 template instantiations
+# ---------------------------------------------------------------------------
+
+VARIANTS_8PH = list(range(13))
+SHAPES_8PH = [
+    (256, 256, 192),    # one tile, T=3 (odd), minimum K: prologue of exactly 7 halves
+    (512, 256, 256),    # T=4
+    (256, 768, 320),    # T=5 (odd-T tail), tiles_n=3, nwg=3 (<8)
+    (768, 768, 192),    # nwg=9 (nwg % 8 != 0, remap remainder path)
+    (1024, 1024, 192),  # nwg=16 (nwg % 8 == 0)
+]
+
+
+@pytest.mark.parametrize("shape", SHAPES_8PH, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("variant", VARIANTS_8PH)
+def test_gemm_bf16_8ph_exact(ext, variant, shape):
+    p = problem("bf16", *shape)
+    run_protocol(
+        lambda out: ext.gemm_bf16_8ph(p["A"], p["Bt"], variant=variant, out=out),
+        p, exact(p), f"gemm_bf16_8ph v{variant} {shape}")
+
+
+@pytest.mark.parametrize("variant", [0, 3, 9, 12])
+def test_gemm_bf16_8ph_real_valued_within_bound(ext, variant):
+    p = problem("bf16_real", 512, 256, 512)
+    worst = run_protocol(
+        lambda out: ext.gemm_bf16_8ph(p["A"], p["Bt"], variant=variant, out=out),
+        p, bounded(p), f"gemm_bf16_8ph v{variant} real")
+    report(f"gemm_bf16_8ph v{variant}", worst)
+
+
+# ---------------------------------------------------------------------------
+# bf16 128^2
+# ---------------------------------------------------------------------------
+
+SHAPES_128 = [
+    (128, 256, 32),    # one BK=32 step, no prefetch (N != M keeps it asymmetric)
+    (128, 128, 32),    # the single-tile form of the same
+    (128, 256, 96),    # BK=32, 3 steps
+    (128, 128, 64),    # one BK=64 step
+    (256, 384, 192),   # BK=64, 3 steps, 6 tiles
+]
+
+
+@pytest.mark.parametrize("shape", SHAPES_128, ids=lambda s: "x".join(map(str, s)))
+def test_gemm_bf16_bt_exact(ext, shape):
+    p = problem("bf16", *shape)
+    run_protocol(lambda out: ext.gemm_bf16_bt(p["A"], p["Bt"], out=out),
+                 p, exact(p), f"gemm_bf16_bt {shape}")
+
+
+@pytest.mark.parametrize("bk", [32, 64])
+def test_gemm_bf16_bt_forced_bk_exact(ext, bk):
+    """gemm_bf16_tflops can time BK=32 at a K that divides by 64; the binding
+    reaches the same instantiation through the same dispatch with bk=."""
+    p = problem("bf16", 256, 384, 192)
+    run_protocol(lambda out: ext.gemm_bf16_bt(p["A"], p["Bt"], bk=bk, out=out),
+                 p, exact(p), f"gemm_bf16_bt bk={bk}")
+
+
+@pytest.mark.parametrize(
+    "shape", [(128, 128, 64), (256, 384, 64), (384, 384, 64), (512, 512, 64),
+              (256, 384, 96)],
+    ids=["1tile", "6tiles", "9tiles", "16tiles", "6tiles-bk32"])
+def test_gemm_bf16_bt_xcd_swizzle_exact(ext, shape):
+    """use_swizzle=1: the bijective XCD remap at nwg < 8, nwg % 8 != 0 and
+    nwg % 8 == 0 — every tile must still be written exactly once, in place."""
+    p = problem("bf16", *shape)
+    run_protocol(
+        lambda out: ext.gemm_bf16_bt(p["A"], p["Bt"], swizzle=1, out=out),
+        p, exact(p), f"gemm_bf16_bt swizzle {shape}")
+
+
+def test_gemm_bf16_bt_real_valued_within_bound(ext):
+    p = problem("bf16_real", 256, 384, 512)
+    worst = run_protocol(lambda out: ext.gemm_bf16_bt(p["A"], p["Bt"], out=out),
+                         p, bounded(p), "gemm_bf16_bt real")
+    report("gemm_bf16_bt", worst)
+
+
+# ---------------------------------------------------------------------------
+# MX fp8
+# ---------------------------------------------------------------------------
+
+FP8_CODES = [16, 17, 18, 20, 32]
+SHAPES_FP8 = [
+    (256, 256, 256),   # T=2, minimum K
+    (512, 256, 384),   # T=3
+    (256, 768, 640),   # T=5, tiles_n=3
+]
+
+
+@pytest.mark.parametrize("shape", SHAPES_FP8, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("code", FP8_CODES)
+def test_gemm_fp8_mx_exact(ext, code, shape):
+    p = problem("e4m3", *shape)
+    run_protocol(
+        lambda out: ext.gemm_fp8_mx(p["A"], p["Bt"], shape=code, out=out),
+        p, exact(p), f"gemm_fp8_mx shape={code} {shape}")
+
+
+@pytest.mark.parametrize("code", FP8_CODES)
+def test_gemm_fp8_mx_full_range_within_bound(ext, code):
+    """Every finite e4m3 code: both zeros, all subnormals, +-448.
+
+    Finding: against the plain K*2^-23 bound every shape code, including the
+    32x32x64 instruction, returns the same bits and misses by the same amount
+    (worst err/bound 1.11 here, 7.96 with crafted operands) while staying
+    bit-exact on the exact set. The cause is the MX-scaled MFMA itself, which
+    truncates products below 2^-13 of the largest of each group of 8
+    (kernel_refs.MX_FP8_TRUNCATION; docs/testing.md). The factor is scaled
+    by exactly that derived term; the test below holds the kernels to the
+    unscaled bound against a reference that models the truncation."""
+    p = problem("e4m3_full", 256, 512, 512)
+    worst = run_protocol(
+        lambda out: ext.gemm_fp8_mx(p["A"], p["Bt"], shape=code, out=out),
+        p,
+        lambda C: kr.assert_within_sum_bound(
+            C, p["ref"], p["a64"].abs(), p["b64"].abs(), p["K"],
+            extra_factor=kr.MX_FP8_TRUNCATION),
+        f"gemm_fp8_mx shape={code} full-range")
+    report(f"gemm_fp8_mx shape={code} (bound incl. MX truncation)", worst)
+
+
+@functools.lru_cache(maxsize=None)
+def truncation_model_problem():
+    p = dict(problem("e4m3_full", 256, 512, 256))
+    p["ref"] = kr.mx_fp8_truncated_reference(p["A"], p["Bt"])
+    return p
+
+
+@pytest.mark.parametrize("code", FP8_CODES)
+def test_gemm_fp8_mx_full_range_matches_truncation_model(ext, code):
+    """Full-range e4m3 against the float64 model of the instruction's
+    group-of-8 product truncation, at the plain K*2^-23 bound: what remains
+    after the documented truncation is fp32 accumulation order only, so a
+    dropped, duplicated or stale element is as visible here as in bf16."""
+    p = truncation_model_problem()
+    worst = run_protocol(
+        lambda out: ext.gemm_fp8_mx(p["A"], p["Bt"], shape=code, out=out),
+        p, bounded(p), f"gemm_fp8_mx shape={code} vs truncation model")
+    report(f"gemm_fp8_mx shape={code} vs truncation model", worst)
+
+
+@pytest.mark.parametrize("code", [16, 32])
+def test_mx_fp8_instruction_truncates_as_documented(ext, code):
+    """The hardware facts behind kernel_refs.MX_FP8_TRUNCATION, asserted on
+    both MX instructions with crafted operands (every expected value is
+    exactly representable, so each assertion is bit-exact): if a future part
+    adds its fp8 products differently this fails and the bound's
+    justification must be revisited, in either direction."""
+    import numpy as np
+
+    def c(v):
+        return int(np.flatnonzero((kr.E4M3_LUT == v)
+                                  & (np.signbit(kr.E4M3_LUT) == np.signbit(v)))[0])
+
+    M = N = K = 256
+    A = np.zeros((M, K), dtype=np.uint8)
+    B = np.zeros((N, K), dtype=np.uint8)
+    B[0, :] = c(1.0); B[0, 0] = B[0, 128] = c(448.0)  # col 0: big product 448*448
+    B[1, :128] = c(1.0)                        # col 1: big product 448*1
+    rows = [                                    # A[i] = [448, small...]; want (col0, col1)
+        ([4.0], 200704.0, 452.0),               # 4 < 2^(16-13): gone next to 448^2
+        ([8.0], 200712.0, 456.0),               # 8 = 2^(16-13): kept
+        ([-4.0], 200704.0, 444.0),              # toward zero, not toward -inf
+        ([2.0 ** -6], 200704.0, 448.0),         # 2^-6 < 2^(8-13): gone next to 448*1
+        ([2.0 ** -5], 200704.0, 448.03125),     # 2^-5 = 2^(8-13): kept
+        ([2.0 ** -9] * 127, 200704.234375, None),  # only the 7 group partners go
+        ([4.0] * 127, 200704.0 + 120 * 4.0, None),  # same, just below the cut
+    ]
+    for i, (small, _, _) in enumerate(rows):
+        A[i, 0] = c(448.0)
+        A[i, 1:1 + len(small)] = [c(s) for s in small]
+    # big product in one 128-wide K block, 128 small ones in the other: the
+    # accumulator input is NOT truncated (it would give 200704.0); the exact
+    # sum 200704 + 0.875 + 127 * 2^-9 rounds to nearest fp32, 200705.125
+    n = len(rows)
+    A[n, 128] = c(448.0); A[n, 0:128] = c(2.0 ** -9)        # small block first
+    A[n + 1, 0] = c(448.0); A[n + 1, 128:256] = c(2.0 ** -9)  # big block first
+    rows += [(["other block"], 200705.125, None)] * 2
+    buf = kr.PoisonedOut(M * N, "cuda", shape=(M, N))
+    ext.gemm_fp8_mx(torch.from_numpy(A).cuda(), torch.from_numpy(B).cuda(),
+                    shape=code, out=buf.out)
+    torch.cuda.synchronize()
+    buf.check(f"gemm_fp8_mx shape={code} crafted")
+    got = buf.out[:len(rows), :2].cpu()
+    for i, (small, want0, want1) in enumerate(rows):
+        assert got[i, 0].item() == want0, (i, small, got[i, 0].item(), want0)
+        if want1 is not None:
+            assert got[i, 1].item() == want1, (i, small, got[i, 1].item(), want1)
+    assert not bool(buf.out[len(rows):].any()) and not bool(buf.out[:, 2:].any())
+
+
+# ---------------------------------------------------------------------------
+# MX fp4
+# ---------------------------------------------------------------------------
+
+FP4_CODES = [16, 17, 18, 19, 21, 32]
+SHAPES_FP4 = [
+    (256, 256, 512),    # T=2, minimum K
+    (512, 256, 768),    # T=3
+    (256, 768, 1280),   # T=5, tiles_n=3
+]
+
+
+@pytest.mark.parametrize("shape", SHAPES_FP4, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("code", FP4_CODES)
+def test_gemm_fp4_mx_exact(ext, code, shape):
+    p = problem("e2m1", *shape)
+    K = shape[2]
+    run_protocol(
+        lambda out: ext.gemm_fp4_mx(p["A"], p["Bt"], K, shape=code, out=out),
+        p, exact(p), f"gemm_fp4_mx shape={code} {shape}")
+
+
+# ---------------------------------------------------------------------------
+# single-tile MFMA wrappers (B is [K][N] here, not transposed)
+# ---------------------------------------------------------------------------
+
+SHAPES_MFMA = {
+    "f32": [(16, 16, 4),      # one wave, three idle in the block
+            (48, 16, 8),      # 3 waves
+            (80, 48, 36)],    # 15 waves in 4 blocks: the last block is partial
+    "bf16": [(16, 16, 32), (48, 16, 64), (80, 48, 96)],
+}
+
+
+@pytest.mark.parametrize(
+    "kernel,shape",
+    [(k, s) for k in ("f32", "bf16") for s in SHAPES_MFMA[k]],
+    ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)))
+def test_mfma_tile_exact(ext, kernel, shape):
+    p = problem(kernel, *shape)
+    B = p["Bt"].T.contiguous()  # [K][N]
+    fn = ext.mfma_f32_matmul if kernel == "f32" else ext.mfma_bf16_matmul
+    run_protocol(lambda out: fn(p["A"], B, out=out), p, exact(p),
+                 f"mfma_{kernel}_matmul {shape}")
+
+
+@pytest.mark.parametrize("kernel,shape", [("f32", (80, 48, 36)), ("bf16", (80, 48, 96))])
+def test_mfma_tile_real_valued_within_bound(ext, kernel, shape):
+    p = problem(kernel + "_real", *shape)
+    B = p["Bt"].T.contiguous()
+    fn = ext.mfma_f32_matmul if kernel == "f32" else ext.mfma_bf16_matmul
+    worst = run_protocol(lambda out: fn(p["A"], B, out=out), p, bounded(p),
+                         f"mfma_{kernel}_matmul real")
+    report(f"mfma_{kernel}_matmul", worst)
+
+
+# ---------------------------------------------------------------------------
+# input handling: views reach the kernel with the same values
+# ---------------------------------------------------------------------------
+
+def _bindings(ext):
+    """(name, kind, shape, call(A, Bt, out)) for the four tiled GEMMs."""
+    return [
+        ("gemm_bf16_bt", "bf16", (256, 384, 192),
+         lambda A, Bt, out: ext.gemm_bf16_bt(A, Bt, out=out)),
+        ("gemm_bf16_8ph", "bf16", (512, 256, 256),
+         lambda A, Bt, out: ext.gemm_bf16_8ph(A, Bt, out=out)),
+        ("gemm_fp8_mx", "e4m3", (512, 256, 384),
+         lambda A, Bt, out: ext.gemm_fp8_mx(A, Bt, out=out)),
+        ("gemm_fp4_mx", "e2m1", (512, 256, 768),
+         lambda A, Bt, out: ext.gemm_fp4_mx(A, Bt, 768, out=out)),
+    ]
+
+
+@pytest.mark.parametrize("which", range(4), ids=["bf16_bt", "bf16_8ph", "fp8", "fp4"])
+def test_views_give_the_same_result_as_contiguous_copies(ext, which):
+    name, kind, shape, call = _bindings(ext)[which]
+    p = problem(kind, *shape)
+    A, Bt = p["A"], p["Bt"]
+    # transposed (non-contiguous) views holding the same values
+    A_t = A.T.contiguous().T
+    Bt_t = Bt.T.contiguous().T
+    assert not A_t.is_contiguous() and torch.equal(A_t, A)
+    run_protocol(lambda out: call(A_t, Bt_t, out), p, exact(p), f"{name} transposed views")
+    # row-slices with a storage offset: contiguous, offset a multiple of 16 B
+    bigA = torch.cat([torch.ones_like(A[:256]), A])
+    bigB = torch.cat([torch.ones_like(Bt[:256]), Bt])
+    A_s, Bt_s = bigA[256:], bigB[256:]
+    assert A_s.storage_offset() > 0 and A_s.is_contiguous()
+    run_protocol(lambda out: call(A_s, Bt_s, out), p, exact(p), f"{name} row-slices")
+
+
+# ---------------------------------------------------------------------------
+# rejection: RuntimeError before any launch
+# ---------------------------------------------------------------------------
+
+def _off_by_one(t):
+    """A contiguous view of the same shape whose data pointer is one element
+    past a 16-byte boundary."""
+    flat = torch.zeros(t.numel() + 8, dtype=t.dtype, device=t.device)
+    v = flat[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 != 0
+    return v
+
+
+def _expect_rejected(call, buf, match=None):
+    """The call raises RuntimeError and nothing was written to `buf`."""
+    buf.poison()
+    with pytest.raises(RuntimeError, match=match):
+        call()
+    torch.cuda.synchronize()
+    assert bool((buf.buf.view(torch.int32) == kr.POISON_BITS).all()), \
+        "a rejected call still wrote to out"
+
+
+def _all_gemm_bindings(ext):
+    """(name, kind, good shape, K below minimum, call(A, B, out), needs [K][N] B)"""
+    tiled = [(n, k, s, c, False) for n, k, s, c in _bindings(ext)]
+    kmin = {"gemm_bf16_bt": 0, "gemm_bf16_8ph": 128, "gemm_fp8_mx": 128,
+            "gemm_fp4_mx": 256}
+    out = [(n, k, s, kmin[n], c, bt) for n, k, s, c, bt in tiled]
+    out.append(("mfma_f32_matmul", "f32", (48, 16, 8), 0,
+                lambda A, B, out: ext.mfma_f32_matmul(A, B, out=out), True))
+    out.append(("mfma_bf16_matmul", "bf16", (48, 16, 64), 0,
+                lambda A, B, out: ext.mfma_bf16_matmul(A, B, out=out), True))
+    return out
+
+
+BINDING_IDS = ["bf16_bt", "bf16_8ph", "fp8", "fp4", "mfma_f32", "mfma_bf16"]
+
+
+def _operands(ext, which, shape=None, K_override=None):
+    name, kind, good, kmin, call, b_is_kn = _all_gemm_bindings(ext)[which]
+    M, N, K = shape or good
+    gen = _GEN[kind]
+    Kgen = max(K, 2)
+    A = gen(M, Kgen, 1)[0].cuda()
+    Bt = gen(N, Kgen, 2)[0].cuda()
+    if K < Kgen:  # K == 0: empty operands
+        A, Bt = A[:, :0].contiguous(), Bt[:, :0].contiguous()
+    B = Bt.T.contiguous() if b_is_kn else Bt
+    if name == "gemm_fp4_mx":
+        call_k = lambda A_, B_, out, c=ext: c.gemm_fp4_mx(A_, B_, K, out=out)
+        return name, A, B, call_k, (M, N, K)
+    return name, A, B, call, (M, N, K)
+
+
+@pytest.mark.parametrize("which", range(6), ids=BINDING_IDS)
+def test_misaligned_pointers_are_rejected_before_launch(ext, which):
+    """The check is made on the pointer; no misaligned launch is ever run."""
+    name, A, B, call, (M, N, K) = _operands(ext, which)
+    buf = kr.PoisonedOut(M * N + 8, "cuda")
+    out = buf.buf[:M * N].view(M, N)
+    bname = "B" if name.startswith("mfma") else "Bt"
+    _expect_rejected(lambda: call(_off_by_one(A), B, out), buf, match="A: data pointer")
+    _expect_rejected(lambda: call(A, _off_by_one(B), out), buf,
+                     match=f"{bname}: data pointer")
+    out_off = buf.buf[1:1 + M * N].view(M, N)
+    assert out_off.is_contiguous() and out_off.data_ptr() % 16 != 0
+    _expect_rejected(lambda: call(A, B, out_off), buf, match="out: data pointer")
+    # and the aligned call is fine
+    call(A, B, out)
+    torch.cuda.synchronize()
+    assert not bool(torch.isnan(out).any())
+
+
+@pytest.mark.parametrize("which", range(6), ids=BINDING_IDS)
+def test_bad_out_is_rejected_before_launch(ext, which):
+    name, A, B, call, (M, N, K) = _operands(ext, which)
+    assert M != N
+    buf = kr.PoisonedOut(2 * M * N, "cuda")
+    # wrong dtype
+    for dt in (torch.float64, torch.bfloat16, torch.int32):
+        bad = torch.zeros(M, N, dtype=dt, device="cuda")
+        _expect_rejected(lambda: call(A, B, bad), buf, match="out: must be float32")
+        assert not bool(bad.bool().any())
+    # wrong shape (transposed extents, 1-D, too large)
+    _expect_rejected(lambda: call(A, B, buf.buf[:M * N].view(N, M)), buf,
+                     match="out: must have shape")
+    _expect_rejected(lambda: call(A, B, buf.buf[:M * N]), buf,
+                     match="out: must have shape")
+    _expect_rejected(lambda: call(A, B, buf.buf[:2 * M * N].view(2 * M, N)), buf,
+                     match="out: must have shape")
+    # non-contiguous: right shape, wrong strides
+    _expect_rejected(lambda: call(A, B, buf.buf[:M * N].view(N, M).T), buf,
+                     match="out: must be contiguous")
+    _expect_rejected(lambda: call(A, B, buf.buf[:2 * M * N].view(M, 2 * N)[:, :N]), buf,
+                     match="out: must be contiguous")
+    # wrong device
+    with pytest.raises(RuntimeError, match="out: must be on the same device"):
+        call(A, B, torch.zeros(M, N, dtype=torch.float32))
+
+
+@pytest.mark.parametrize("which", range(6), ids=BINDING_IDS)
+def test_bad_extents_are_rejected_before_launch(ext, which):
+    name, kind, (M, N, K), kmin, _, _ = _all_gemm_bindings(ext)[which]
+    step = {"gemm_bf16_bt": (128, 128, 32), "gemm_bf16_8ph": (256, 256, 64),
+            "gemm_fp8_mx": (256, 256, 128), "gemm_fp4_mx": (256, 256, 256),
+            "mfma_f32_matmul": (16, 16, 4), "mfma_bf16_matmul": (16, 16, 32)}[name]
+    sub = {"gemm_bf16_bt": 16, "gemm_bf16_8ph": 128, "gemm_fp8_mx": 128,
+           "gemm_fp4_mx": 128, "mfma_f32_matmul": 8, "mfma_bf16_matmul": 8}[name]
+    ksub = {"gemm_bf16_bt": 16, "gemm_bf16_8ph": 32, "gemm_fp8_mx": 64,
+            "gemm_fp4_mx": 128, "mfma_f32_matmul": 2, "mfma_bf16_matmul": 16}[name]
+    cases = [
+        (M, N, kmin),           # K below the minimum
+        (M + sub, N, K),        # M off the tile multiple
+        (M, N + sub, K),        # N off the tile multiple
+        (M, N, K + ksub),       # K off the K-step multiple
+    ]
+    for shape in cases:
+        _, A, B, call, (m, n, k) = _operands(ext, which, shape=shape)
+        buf = kr.PoisonedOut(m * n, "cuda", shape=(m, n))
+        _expect_rejected(lambda: call(A, B, buf.out), buf, match="multiple")
+
+
+def test_unknown_variant_and_shape_codes_are_rejected(ext):
+    p = problem("bf16", 512, 256, 256)
+    buf = kr.PoisonedOut(512 * 256, "cuda", shape=(512, 256))
+    for v in (-1, 13):
+        _expect_rejected(lambda: ext.gemm_bf16_8ph(p["A"], p["Bt"], variant=v, out=buf.out),
+                         buf, match="unknown 8-phase variant")
+    p8 = problem("e4m3", 512, 256, 384)
+    for code in (0, 19, 21, 33):
+        _expect_rejected(lambda: ext.gemm_fp8_mx(p8["A"], p8["Bt"], shape=code, out=buf.out),
+                         buf, match="unknown fp8 MX shape code")
+    p4 = problem("e2m1", 512, 256, 768)
+    for code in (0, 20, 33):
+        _expect_rejected(
+            lambda: ext.gemm_fp4_mx(p4["A"], p4["Bt"], 768, shape=code, out=buf.out),
+            buf, match="unknown fp4 MX shape code")
+    with pytest.raises(RuntimeError, match="unknown fp8 MX shape code"):
+        ext.gemm_fp8_mx_tflops(0, 256, 1, 19)
+    with pytest.raises(RuntimeError, match="unknown fp4 MX shape code"):
+        ext.gemm_fp4_mx_tflops(0, 256, 1, 20)
+    with pytest.raises(RuntimeError, match="unknown 8-phase variant"):
+        ext.gemm_bf16_8ph_tflops(0, 256, 1, 13)
+
+
+# ---------------------------------------------------------------------------
+# copy
+# ---------------------------------------------------------------------------
+
+# the smallest size that enters copy_f32x4_x4_kernel (n4 >= 4 * 32768 * 256),
+# plus 1000 float4 for that kernel's remainder loop and 3 floats of scalar tail
+BIG_COPY = 134217728 + 4 * 1000 + 3
+COPY_SIZES = [0, 1, 2, 3, 4, 5, 1023, 1024, (1 << 20) + 3, BIG_COPY]
+
+
+@pytest.mark.parametrize("n", COPY_SIZES)
+def test_copy_f32_bit_exact(ext, n):
+    # position pattern: element i holds the bits of int32 i, so a displaced
+    # chunk is identifiable (i < 2^28 reads as a finite float, never as NaN)
+    src = torch.arange(n, dtype=torch.int32, device="cuda").view(torch.float32)
+    buf = kr.PoisonedOut(n, "cuda")
+    ext.copy_f32(buf.out, src)
+    torch.cuda.synchronize()
+    assert buf.guard_intact(), f"n={n}: guard behind dst was overwritten"
+    got = buf.out.view(torch.int32)
+    want = src.view(torch.int32)
+    if not torch.equal(got, want):
+        bad = torch.nonzero(got != want).flatten()
+        first = int(bad[0])
+        raise AssertionError(
+            f"n={n}: {bad.numel()} elements differ, first at {first} "
+            f"(float4 #{first // 4}): got bits {int(got[first]):#x}, want {first:#x}")
+
+
+def test_copy_f32_offset_by_one_views_are_rejected(ext):
+    n = 1024
+    src = torch.arange(n + 8, dtype=torch.int32, device="cuda").view(torch.float32)
+    buf = kr.PoisonedOut(n + 8, "cuda")
+    _expect_rejected(lambda: ext.copy_f32(buf.buf[:n], src[1:1 + n]), buf,
+                     match="src: data pointer")
+    _expect_rejected(lambda: ext.copy_f32(buf.buf[1:1 + n], src[:n]), buf,
+                     match="dst: data pointer")
+    ext.copy_f32(buf.buf[4:4 + n], src[4:4 + n])  # 16-byte offsets are fine
+    torch.cuda.synchronize()
+    assert torch.equal(buf.buf[4:4 + n].view(torch.int32), src[4:4 + n].view(torch.int32))
