@@ -4,6 +4,7 @@ Artifacts (git-ignored, but shipped by the repo snapshot to GPU boxes):
 
   gpu_docker_api_amd/ops/_hipcore.so   - torch extension (csrc/hipcore.hip)
   gpu_docker_api_amd/ops/_iocopy.so    - pybind11 module (csrc/iocopy.cpp)
+  gpu_docker_api_amd/ops/_proclife.so  - pybind11 module (csrc/proclife.cpp)
   csrc/bin/rccl_smoke                  - standalone binary (csrc/rccl_smoke.hip)
 
 Run: ``python -m gpu_docker_api_amd.ops.build`` (or __graft_entry__.build()).
@@ -103,6 +104,31 @@ def build_iocopy(force: bool = False) -> str:
     return out
 
 
+def build_proclife(force: bool = False) -> str:
+    src = os.path.join(CSRC, "proclife.cpp")
+    core = os.path.join(CSRC, "proclife_core.h")
+    out = os.path.join(OPS, "_proclife.so")
+    if not force and _newer(out, src, core):
+        return out
+    import pybind11
+
+    py_inc = sysconfig.get_paths()["include"]
+    cmd = [
+        "g++",
+        "-O2",
+        "-std=c++17",
+        "-fPIC",
+        "-shared",
+        src,
+        "-o",
+        out,
+        f"-I{pybind11.get_include()}",
+        f"-I{py_inc}",
+    ]
+    _run(cmd)
+    return out
+
+
 def build_rccl_smoke(force: bool = False) -> str:
     src = os.path.join(CSRC, "rccl_smoke.hip")
     out = os.path.join(BIN, "rccl_smoke")
@@ -128,6 +154,7 @@ def build_rccl_smoke(force: bool = False) -> str:
 def build_all(force: bool = False) -> dict:
     return {
         "iocopy": build_iocopy(force),
+        "proclife": build_proclife(force),
         "hipcore": build_hipcore(force),
         "rccl_smoke": build_rccl_smoke(force),
     }

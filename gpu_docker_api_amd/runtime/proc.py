@@ -34,6 +34,7 @@ import uuid as uuidlib
 from typing import Dict, List, Optional
 
 from ..models.etcd import ContainerSpec
+from ..ops import proclife
 from ..utils.names import safe_subpath
 from ..xerrors import ContainerExisted, ContainerNotExist, VolumeExisted
 from .base import ContainerState, GpuResolver, RuntimeDriver, VolumeState
@@ -44,12 +45,21 @@ log = logging.getLogger(__name__)
 CGROUP_ROOT = "/sys/fs/cgroup"
 DEFAULT_CMD = ["sleep", "infinity"]
 
+# spawn/reap/teardown run in ops/_proclife.so when it is built and
+# GDA_NATIVE_LIFECYCLE does not force the Python path (ops/proclife.py)
+NATIVE_LIFECYCLE = proclife.enabled()
+if proclife.ENABLED and not NATIVE_LIFECYCLE:  # never a silent fallback
+    log.warning("native lifecycle module not loaded (%s): using the Python path",
+                proclife.load_error())
+
 
 class _Proc:
     def __init__(self, state: ContainerState, spec: ContainerSpec) -> None:
         self.state = state
         self.spec = spec
-        self.popen: Optional[subprocess.Popen] = None
+        # a subprocess.Popen or a native proclife Child: only .pid and
+        # .poll() are used (plus .fileno() on a Child, to await its exit)
+        self.popen = None
         self.cgroup: Optional[str] = None
         # restart policy (reference containers run unless-stopped,
         # services/replicaset.go:73-75; dockerd enforces it there — here the
@@ -69,6 +79,9 @@ class _Proc:
         self.attached_start = 0
         self.was_started = False
         self.start_ticks = 0  # cached /proc starttime of the live leader
+        # futures of the stop() calls awaiting the leader's exit on its pidfd
+        # (one loop reader serves them all: add_reader keeps one per fd)
+        self.exit_waiters: List[asyncio.Future] = []
 
 
 class ProcRuntime(RuntimeDriver):
@@ -80,7 +93,13 @@ class ProcRuntime(RuntimeDriver):
         gpu_resolver: Optional[GpuResolver] = None,
         use_cgroups: bool = True,
         loop_volumes: bool = False,
+        native: Optional[bool] = None,
     ) -> None:
+        # native=False forces the Python lifecycle path for this runtime,
+        # None follows the module default
+        if native is None:
+            native = NATIVE_LIFECYCLE
+        self._nat = proclife if native and proclife.available() else None
         self.base = base_dir or os.path.join(os.getcwd(), ".state", "procrt")
         for sub in ("containers", "volumes", "images", "trash"):
             os.makedirs(os.path.join(self.base, sub), exist_ok=True)
@@ -243,8 +262,12 @@ class ProcRuntime(RuntimeDriver):
                 "running": p.state.running,
                 "restarts": p.restarts,
             }
-            with open(os.path.join(self._cdir(p.state.name), "meta.json"), "w") as f:
-                json.dump(meta, f)
+            path = os.path.join(self._cdir(p.state.name), "meta.json")
+            if self._nat is not None:
+                self._nat.write_file(path, json.dumps(meta))
+            else:
+                with open(path, "w") as f:
+                    json.dump(meta, f)
         except OSError:
             pass
 
@@ -324,16 +347,22 @@ class ProcRuntime(RuntimeDriver):
         if name in self._procs:
             raise ContainerExisted(name)
         cid = uuidlib.uuid4().hex[:12]
-        rootfs = os.path.join(self._cdir(name), "rootfs")
-        os.makedirs(rootfs, exist_ok=True)
+        cdir = self._cdir(name)
+        rootfs = os.path.join(cdir, "rootfs")
         seed = self._image_dir(spec.image) if spec.image else ""
-        if seed and os.path.isdir(seed):
+        seeded = bool(seed) and os.path.isdir(seed)
+        binds = list(spec.host_config.get("Binds") or [])
+        # nothing to materialize (the common case): the native module makes
+        # the directories and writes spec.json in one call further down
+        one_call = self._nat is not None and not seeded and not binds
+        if not one_call:
+            os.makedirs(rootfs, exist_ok=True)
+        if seeded:
             # image materialization can be large: off the event loop
             await asyncio.get_running_loop().run_in_executor(
                 None, lambda: shutil.copytree(seed, rootfs, dirs_exist_ok=True)
             )
         # bind volumes/host dirs into the rootfs by symlink
-        binds = list(spec.host_config.get("Binds") or [])
         for b in binds:
             src, _, dest = b.partition(":")
             dest = dest.split(":")[0]
@@ -359,9 +388,14 @@ class ProcRuntime(RuntimeDriver):
             binds=binds,
         )
         p = _Proc(st, spec)
+        if one_call:
+            self._nat.prepare_container_dir(cdir, spec.serialize())
         self._procs[name] = p
-        with open(os.path.join(self._cdir(name), "spec.json"), "w") as f:
-            f.write(spec.serialize())
+        if self._nat is None:
+            with open(os.path.join(cdir, "spec.json"), "w") as f:
+                f.write(spec.serialize())
+        elif not one_call:
+            self._nat.write_file(os.path.join(cdir, "spec.json"), spec.serialize())
         # meta (pid identity) is written at start(); a created-not-started
         # container needs none
         return cid
@@ -373,17 +407,40 @@ class ProcRuntime(RuntimeDriver):
 
     _base_env: Optional[Dict[str, str]] = None
 
-    def _env_for(self, p: _Proc) -> Dict[str, str]:
+    @staticmethod
+    def _base_snapshot() -> Dict[str, str]:
         # snapshot os.environ once: copying ~100 vars per container start
         # showed up in the cycle CPU profile
         if ProcRuntime._base_env is None:
             ProcRuntime._base_env = dict(os.environ)
-        env = dict(ProcRuntime._base_env)
-        env.update(visible_device_env(p.state.gpu_uuids, self.gpu_resolver))
+        return ProcRuntime._base_env
+
+    def _env_overrides(self, p: _Proc) -> Dict[str, str]:
+        """What a container's environment adds to the base: the visible
+        device variables, then the spec's Env (later entries win)."""
+        env = dict(visible_device_env(p.state.gpu_uuids, self.gpu_resolver))
         for e in p.state.env:
             k, _, v = e.partition("=")
             env[k] = v
         return env
+
+    def _env_for(self, p: _Proc) -> Dict[str, str]:
+        env = dict(self._base_snapshot())
+        env.update(self._env_overrides(p))
+        return env
+
+    def _spawn_native(self, name: str, p: _Proc, cmd: List[str]):
+        # the base environment is encoded once inside the module; a spawn
+        # carries only the overrides and the merge happens natively
+        base = self._base_snapshot()
+        if not self._nat.base_env_is(base):
+            self._nat.set_base_env(base)
+        return self._nat.spawn(
+            cmd,
+            p.state.upper_dir,
+            self._env_overrides(p),
+            os.path.join(self._cdir(name), "console.log"),
+        )
 
     @staticmethod
     def _enable_controllers(path: str) -> None:
@@ -446,22 +503,28 @@ class ProcRuntime(RuntimeDriver):
         # pool re-measured in round 2: 256 -> 211 single-tenant, 258 -> 243
         # at 8 tenants, bench p50 4.5 -> 5.0 ms) loses more to the thread
         # hop than the freed loop time buys — keep it inline
-        logf = open(os.path.join(self._cdir(name), "console.log"), "ab")
-        try:
-            p.popen = subprocess.Popen(
-                cmd,
-                cwd=p.state.upper_dir,
-                env=self._env_for(p),
-                stdout=logf,
-                stderr=subprocess.STDOUT,
-                start_new_session=True,  # own pgid: exact-target signalling
-            )
-        finally:
-            logf.close()
+        if self._nat is not None:
+            # vfork+execve, pidfd and the /proc start time in one native call
+            p.popen = self._spawn_native(name, p, cmd)
+            start_ticks = p.popen.starttime
+        else:
+            logf = open(os.path.join(self._cdir(name), "console.log"), "ab")
+            try:
+                p.popen = subprocess.Popen(
+                    cmd,
+                    cwd=p.state.upper_dir,
+                    env=self._env_for(p),
+                    stdout=logf,
+                    stderr=subprocess.STDOUT,
+                    start_new_session=True,  # own pgid: exact-target signalling
+                )
+            finally:
+                logf.close()
+            start_ticks = self._proc_starttime(p.popen.pid) or 0
         p.attached_pid = 0
         p.was_started = True
         p.last_start_at = time.monotonic()
-        p.start_ticks = self._proc_starttime(p.popen.pid) or 0
+        p.start_ticks = start_ticks
         p.state.pid = p.popen.pid
         p.state.running, p.state.paused, p.state.status = True, False, "running"
         self._setup_cgroup(name, p, p.popen.pid)
@@ -475,6 +538,62 @@ class ProcRuntime(RuntimeDriver):
         except ProcessLookupError:
             pass
 
+    @staticmethod
+    def _has_pidfd(p: _Proc) -> bool:
+        return p.popen is not None and not isinstance(p.popen, subprocess.Popen)
+
+    async def _await_exit(self, p: _Proc, fd: int, timeout: float) -> bool:
+        """Wait until the child behind pidfd ``fd`` has exited or ``timeout``
+        seconds have passed; True when it is gone (and reaped). The reader
+        and the timeout handle always come off the loop again."""
+        loop = asyncio.get_running_loop()
+        fut = loop.create_future()
+
+        def wake(futs) -> None:
+            for f in futs:
+                if not f.done():
+                    f.set_result(None)
+
+        waiters = p.exit_waiters
+        if not waiters:
+            loop.add_reader(fd, wake, waiters)
+        waiters.append(fut)
+        timer = loop.call_later(timeout, wake, (fut,))
+        try:
+            await fut
+        finally:
+            timer.cancel()
+            waiters.remove(fut)
+            if not waiters:
+                loop.remove_reader(fd)
+        return not self._alive(p)
+
+    async def _poll_exit(self, p: _Proc, timeout: float) -> None:
+        """Polling reap for children without a pidfd: the Python path's
+        Popen, and processes adopted after a daemon restart."""
+        # most processes exit within microseconds of SIGTERM, but
+        # asyncio.sleep(dt) rounds up to the epoll timer granularity
+        # (~1 ms). sleep(0) yields to ready tasks WITHOUT arming a
+        # timer, so this poll loop is both sub-ms for the common case
+        # and cooperative under concurrency (a blocking spin here
+        # measurably cut 8-tenant throughput)
+        spin_until = time.monotonic() + 0.002
+        while time.monotonic() < spin_until and self._alive(p):
+            await asyncio.sleep(0)
+        deadline = time.monotonic() + timeout
+        delay = 0.001  # timer-based backoff for the slow case
+        while time.monotonic() < deadline and self._alive(p):
+            await asyncio.sleep(delay)
+            delay = min(delay * 2, 0.02)
+        if self._alive(p):
+            self._signal_group(p, signal.SIGKILL)
+            # reap without blocking the event loop: a process stuck in
+            # D-state I/O would otherwise stall every handler for 5 s
+            # (ADVICE r1 #5)
+            kill_deadline = time.monotonic() + 5
+            while time.monotonic() < kill_deadline and self._alive(p):
+                await asyncio.sleep(0.005)
+
     async def stop(self, name: str, timeout: int = 10, _removing: bool = False) -> None:
         p = self._get(name)
         p.manually_stopped = True
@@ -484,28 +603,16 @@ class ProcRuntime(RuntimeDriver):
             # a paused (SIGSTOPped) group keeps SIGTERM pending forever:
             # continue it so termination can be delivered (docker semantics)
             self._signal_group(p, signal.SIGCONT)
-            # most processes exit within microseconds of SIGTERM, but
-            # asyncio.sleep(dt) rounds up to the epoll timer granularity
-            # (~1 ms). sleep(0) yields to ready tasks WITHOUT arming a
-            # timer, so this poll loop is both sub-ms for the common case
-            # and cooperative under concurrency (a blocking spin here
-            # measurably cut 8-tenant throughput)
-            spin_until = time.monotonic() + 0.002
-            while time.monotonic() < spin_until and self._alive(p):
-                await asyncio.sleep(0)
-            deadline = time.monotonic() + timeout
-            delay = 0.001  # timer-based backoff for the slow case
-            while time.monotonic() < deadline and self._alive(p):
-                await asyncio.sleep(delay)
-                delay = min(delay * 2, 0.02)
-            if self._alive(p):
-                self._signal_group(p, signal.SIGKILL)
-                # reap without blocking the event loop: a process stuck in
-                # D-state I/O would otherwise stall every handler for 5 s
-                # 
-                kill_deadline = time.monotonic() + 5
-                while time.monotonic() < kill_deadline and self._alive(p):
-                    await asyncio.sleep(0.005)
+            child_fd = p.popen.fileno() if self._has_pidfd(p) else -1
+            if child_fd >= 0:
+                # natively spawned: the pidfd turns readable the moment the
+                # leader exits, so the handler sleeps in the loop's own epoll
+                # and wakes exactly then — no polling, no timer granularity
+                if not await self._await_exit(p, child_fd, timeout):
+                    self._signal_group(p, signal.SIGKILL)
+                    await self._await_exit(p, child_fd, 5)
+            else:
+                await self._poll_exit(p, timeout)
         leader = self._leader_pid(p)
         if leader:
             # the leader is gone; sweep any group stragglers (orphaned
@@ -531,6 +638,15 @@ class ProcRuntime(RuntimeDriver):
             except OSError:
                 pass
         self._signal_group(p, signal.SIGSTOP)
+        # the stop lands when the leader is next scheduled, not when kill()
+        # returns: wait (bounded) until /proc shows it, so "paused" is true
+        # by the time it is reported — a daemon restarted right after would
+        # otherwise adopt the container as running
+        leader = self._leader_pid(p)
+        for _ in range(50):
+            if not leader or self._proc_stat(leader)[0] in ("T", "t", None):
+                break
+            await asyncio.sleep(0.002)
         p.state.paused, p.state.status = True, "paused"
 
     async def unpause(self, name: str) -> None:
@@ -571,7 +687,10 @@ class ProcRuntime(RuntimeDriver):
         # chaos soak spiraled its last quarter to 42 ms p50 as the doomed
         # backlog outgrew the deleter. Inline is self-limiting and held
         # 252 cycles/s flat over the same soak for ~0.07 ms extra p50.
-        shutil.rmtree(cdir, ignore_errors=True)
+        if self._nat is not None:
+            self._nat.remove_tree(cdir)  # containment-checked by _cdir
+        else:
+            shutil.rmtree(cdir, ignore_errors=True)
 
     async def inspect(self, name: str) -> Optional[ContainerState]:
         p = self._procs.get(name)

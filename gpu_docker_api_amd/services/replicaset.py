@@ -40,6 +40,7 @@ from ..state.keys import Resource
 from ..state.store import StateStore
 from ..state.workqueue import WorkQueue
 from ..utils.copy import CopyEngine
+from ..utils.files import remove_tree
 from ..utils.names import safe_subpath
 from ..utils.timing import PhaseTimer
 from ..state.keys import RELEASED_SET_KEY
@@ -388,7 +389,7 @@ class ReplicaSetService:
             try:
                 if getattr(self.runtime, "owns_rootfs", False):
                     os.makedirs(os.path.dirname(merge_path), exist_ok=True)
-                    shutil.rmtree(merge_path, ignore_errors=True)
+                    remove_tree(merge_path)
                     try:
                         os.rename(old_state.upper_dir, merge_path)
                     except OSError:  # cross-device: fall back to copying
@@ -426,7 +427,7 @@ class ReplicaSetService:
         entries.sort(reverse=True)
         for _v, vname, path in entries[keep:]:
             self.merges.remove(vname)
-            shutil.rmtree(path, ignore_errors=True)
+            remove_tree(path)
 
     @staticmethod
     def _host_ports(state: ContainerState) -> List[int]:

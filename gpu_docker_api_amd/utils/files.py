@@ -2,6 +2,9 @@
 from __future__ import annotations
 
 import os
+import shutil
+
+from ..ops import proclife
 
 
 def dir_size(path: str) -> int:
@@ -23,3 +26,13 @@ def dir_size(path: str) -> int:
 
 def is_dir(path: str) -> bool:
     return os.path.isdir(path)
+
+
+def remove_tree(path: str) -> None:
+    """``shutil.rmtree(path, ignore_errors=True)``, done by the native
+    lifecycle module (descriptor-relative unlinkat walk, GIL released) when
+    it is loaded. Callers containment-check ``path`` first (safe_subpath)."""
+    if proclife.enabled():
+        proclife.remove_tree(path)
+    else:
+        shutil.rmtree(path, ignore_errors=True)
