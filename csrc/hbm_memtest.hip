@@ -1,0 +1,575 @@
+// HBM pattern memory test for the GPU burn-in (MI355X / gfx950).
+//
+// The throughput tiers of /gpus/validate never look at the data they move.
+// This file writes a seeded pattern over a buffer, reads it back and reports
+// every 64-bit word that differs: a weak HBM stack, a stuck bit or an
+// aliasing address line shows here and nowhere else.
+//
+// The unit is the 64-bit word. Word g (a global u64 index: base_word plus
+// the position in the buffer) holds, for a u64 seed:
+//
+//   fmix32(h): h^=h>>16; h*=0x85EBCA6B; h^=h>>13; h*=0xC2B2AE35; h^=h>>16
+//
+//   "addr":  w = g ^ seed                     (address-in-address: aliasing)
+//   "rand":  x = g ^ seed; a = (u32)x; b = (u32)(x >> 32)
+//            lo = fmix32(a + b*0x9E3779B9)
+//            hi = fmix32(~a + b*0x85EBCA77 + 0x27D4EB2F)
+//            w  = (u64)hi << 32 | lo          (every bit toggles: stuck cells)
+//   "zero":  w = 0                            (scrub)
+//   invert:  w = ~w
+//
+// One templated kernel, three modes: write, verify, verify_flip (verify,
+// then store the complement of the EXPECTED word, so a transient error is
+// reported once and a stuck cell again by the next verify).
+//
+// Access shape (CDNA4 guide §2): the 16-byte-aligned body moves 16 B per
+// lane, 1 KiB per wave instruction. A workgroup walks tiles of
+// kBlock * kUnroll vectors; a full tile issues its kUnroll independent
+// loads before the first compare (as copy_f32x4_x4_kernel does), and the
+// grid strides over tiles with a cap of kMaxGrid workgroups (8 per CU on a
+// 256-CU chip). The buffer is only guaranteed 8-byte aligned: a leading and
+// a trailing odd word are handled word by word in the same launch. Every
+// index and byte offset is 64-bit.
+//
+// Included by hipcore.hip (needs HIP_CHECK and the torch headers).
+
+namespace hbm_memtest {
+
+using u32 = unsigned int;
+using u64 = unsigned long long;
+
+constexpr int kBlock = 256;
+constexpr int kUnroll = 4;                    // 16-B vectors per lane per tile
+constexpr int kWordsPerThreadIter = 2 * kUnroll;
+constexpr int kMaxGrid = 2048;
+constexpr u64 kTileVecs = (u64)kBlock * kUnroll;
+
+enum Mode { kWrite = 0, kVerify = 1, kVerifyFlip = 2 };
+enum Pattern { kAddr = 0, kRand = 1, kZero = 2 };
+
+// Device-side report, all u64: [0] mismatching words, [1] OR of
+// expected^actual, [2] record slots claimed, then cap records {g, expected,
+// actual}.
+constexpr int kRepErrors = 0, kRepBits = 1, kRepClaimed = 2, kRepHeader = 3;
+constexpr u64 kMaxRecordsLimit = 65536;
+
+__device__ inline u32 fmix32(u32 h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+// The two b-dependent terms of "rand". b is the upper half of g ^ seed and
+// changes once per 2^32 words, so a tile that does not straddle a multiple
+// of 2^32 computes them once, wave-uniformly: two of the six multiplies per
+// word leave the per-lane work.
+struct HiTerms {
+  u32 p, q;
+  bool uniform;  // p, q hold for every word of the tile
+  __device__ inline void set(u32 b) {
+    p = b * 0x9E3779B9u;
+    q = b * 0x85EBCA77u + 0x27D4EB2Fu;
+  }
+};
+
+__device__ inline u64 rand_word(u32 a, u32 p, u32 q) {
+  u32 lo = fmix32(a + p);
+  u32 hi = fmix32(~a + q);
+  return ((u64)hi << 32) | lo;
+}
+
+// Expected value of the single word g.
+template <int PAT>
+__device__ inline u64 pattern_word(u64 g, u64 seed, u64 inv) {
+  if (PAT == kZero) return inv;
+  u64 x = g ^ seed;
+  if (PAT == kAddr) return x ^ inv;
+  HiTerms t;
+  t.set((u32)(x >> 32));
+  return rand_word((u32)x, t.p, t.q) ^ inv;
+}
+
+// Terms for the words [g_first, g_first + nwords); every argument is
+// wave-uniform, so the branch on .uniform is a scalar one.
+__device__ inline HiTerms tile_terms(u64 g_first, u64 nwords, u64 seed) {
+  HiTerms t;
+  t.uniform = (g_first >> 32) == ((g_first + (nwords - 1)) >> 32);
+  t.set((u32)((g_first ^ seed) >> 32));
+  return t;
+}
+
+// Expected values of the two words g0, g0 + 1 of one 16-byte vector.
+template <int PAT>
+__device__ inline void pattern_pair(u64 g0, u64 seed, u64 inv,
+                                    const HiTerms& t, u64& w0, u64& w1) {
+  if (PAT == kRand && t.uniform) {
+    const u32 sl = (u32)seed, l0 = (u32)g0;
+    w0 = rand_word(l0 ^ sl, t.p, t.q) ^ inv;
+    w1 = rand_word((l0 + 1u) ^ sl, t.p, t.q) ^ inv;
+  } else {
+    w0 = pattern_word<PAT>(g0, seed, inv);
+    w1 = pattern_word<PAT>(g0 + 1, seed, inv);
+  }
+}
+
+// Mismatch slow path: one claim atomic per bad word, and only while the
+// claim counter is still below the cap, so a badly broken card stops
+// issuing them once the records are full.
+__device__ __noinline__ void record_mismatch(u64* rep, u64 cap, u64 g,
+                                             u64 expected, u64 actual) {
+  if (cap == 0) return;
+  u64 claimed = __hip_atomic_load(&rep[kRepClaimed], __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT);
+  if (claimed >= cap) return;
+  u64 slot = atomicAdd(&rep[kRepClaimed], 1ull);
+  if (slot >= cap) return;
+  u64* r = rep + kRepHeader + 3 * slot;
+  r[0] = g;
+  r[1] = expected;
+  r[2] = actual;
+}
+
+__device__ inline void check_word(u64* rep, u64 cap, u64 g, u64 expected,
+                                  u64 actual, u32& cnt, u64& bits) {
+  u64 d = expected ^ actual;
+  if (d != 0) {
+    ++cnt;
+    bits |= d;
+    record_mismatch(rep, cap, g, expected, actual);
+  }
+}
+
+template <int MODE, int PAT>
+__device__ inline void do_word(u64* p, u64 g, u64 seed, u64 inv, u64* rep,
+                               u64 cap, u32& cnt, u64& bits) {
+  u64 e = pattern_word<PAT>(g, seed, inv);
+  if (MODE == kWrite) {
+    *p = e;
+    return;
+  }
+  u64 a = *p;
+  check_word(rep, cap, g, e, a, cnt, bits);
+  if (MODE == kVerifyFlip) *p = ~e;
+}
+
+template <int MODE, int PAT>
+__global__ __launch_bounds__(kBlock) void memtest_kernel(
+    u64* __restrict__ p, u64 n, u64 base, u64 seed, u64 inv,
+    u64* __restrict__ rep, u64 cap) {
+  const u64 head = ((reinterpret_cast<uintptr_t>(p) & 8) != 0 && n > 0) ? 1 : 0;
+  const u64 nvec = (n - head) >> 1;
+  const bool tail = ((n - head) & 1) != 0;
+  ulonglong2* __restrict__ v = reinterpret_cast<ulonglong2*>(p + head);
+  const u64 gbody = base + head;
+  const u64 ntiles = (nvec + kTileVecs - 1) / kTileVecs;
+
+  u32 cnt = 0;   // mismatching words seen by this lane
+  u64 bits = 0;  // OR of expected ^ actual seen by this lane
+
+  for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const u64 v0 = t * kTileVecs + threadIdx.x;
+    const HiTerms hi =
+        tile_terms(gbody + 2 * t * kTileVecs, 2 * kTileVecs, seed);
+    if ((t + 1) * kTileVecs <= nvec) {
+      ulonglong2 a[kUnroll];
+      if (MODE != kWrite) {
+#pragma unroll
+        for (int j = 0; j < kUnroll; ++j) a[j] = v[v0 + (u64)j * kBlock];
+      }
+#pragma unroll
+      for (int j = 0; j < kUnroll; ++j) {
+        const u64 vi = v0 + (u64)j * kBlock;
+        const u64 g0 = gbody + 2 * vi;
+        ulonglong2 e;
+        pattern_pair<PAT>(g0, seed, inv, hi, e.x, e.y);
+        if (MODE == kWrite) {
+          v[vi] = e;
+        } else {
+          if (((a[j].x ^ e.x) | (a[j].y ^ e.y)) != 0) {
+            check_word(rep, cap, g0, e.x, a[j].x, cnt, bits);
+            check_word(rep, cap, g0 + 1, e.y, a[j].y, cnt, bits);
+          }
+          if (MODE == kVerifyFlip) {
+            e.x = ~e.x;
+            e.y = ~e.y;
+            v[vi] = e;
+          }
+        }
+      }
+    } else {
+      // last, partial tile: every vector bounds-checked
+      for (int j = 0; j < kUnroll; ++j) {
+        const u64 vi = v0 + (u64)j * kBlock;
+        if (vi >= nvec) break;
+        const u64 g0 = gbody + 2 * vi;
+        ulonglong2 e;
+        pattern_pair<PAT>(g0, seed, inv, hi, e.x, e.y);
+        if (MODE == kWrite) {
+          v[vi] = e;
+        } else {
+          ulonglong2 a = v[vi];
+          check_word(rep, cap, g0, e.x, a.x, cnt, bits);
+          check_word(rep, cap, g0 + 1, e.y, a.y, cnt, bits);
+          if (MODE == kVerifyFlip) {
+            e.x = ~e.x;
+            e.y = ~e.y;
+            v[vi] = e;
+          }
+        }
+      }
+    }
+  }
+
+  // the odd words either side of the 16-byte-aligned body
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0 && head)
+      do_word<MODE, PAT>(p, base, seed, inv, rep, cap, cnt, bits);
+    if (threadIdx.x == 1 && tail)
+      do_word<MODE, PAT>(p + (n - 1), base + (n - 1), seed, inv, rep, cap, cnt,
+                         bits);
+  }
+
+  if (MODE != kWrite) {
+    // per-wave reduction, then at most one atomic pair per wave, and none
+    // from a wave that saw no mismatch
+    u64 c = cnt;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      c += __shfl_xor(c, off, 64);
+      bits |= __shfl_xor(bits, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0 && c != 0) {
+      atomicAdd(&rep[kRepErrors], c);
+      atomicOr(&rep[kRepBits], bits);
+    }
+  }
+}
+
+template <int MODE>
+void launch_mode(int pat, dim3 grid, hipStream_t s, u64* p, u64 n, u64 base,
+                 u64 seed, u64 inv, u64* rep, u64 cap) {
+  switch (pat) {
+    case kAddr:
+      hipLaunchKernelGGL((memtest_kernel<MODE, kAddr>), grid, dim3(kBlock), 0, s,
+                         p, n, base, seed, inv, rep, cap);
+      break;
+    case kRand:
+      hipLaunchKernelGGL((memtest_kernel<MODE, kRand>), grid, dim3(kBlock), 0, s,
+                         p, n, base, seed, inv, rep, cap);
+      break;
+    case kZero:
+      hipLaunchKernelGGL((memtest_kernel<MODE, kZero>), grid, dim3(kBlock), 0, s,
+                         p, n, base, seed, inv, rep, cap);
+      break;
+    default:
+      TORCH_CHECK(false, "unknown memtest pattern code ", pat);
+  }
+}
+
+// The one launch path, shared by the tensor bindings and the driver. rep may
+// be null for kWrite only.
+void launch(int mode, int pat, u64* p, u64 n, u64 base, u64 seed, bool invert,
+            u64* rep, u64 cap, hipStream_t s) {
+  if (n == 0) return;
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 7) == 0,
+              "memtest: buffer must be 8-byte aligned");
+  TORCH_CHECK(mode == kWrite || rep != nullptr, "memtest: verify needs a report");
+  const u64 head = (reinterpret_cast<uintptr_t>(p) & 8) ? 1 : 0;
+  const u64 nvec = (n - head) >> 1;
+  const u64 ntiles = (nvec + kTileVecs - 1) / kTileVecs;
+  dim3 grid((unsigned)std::min<u64>(std::max<u64>(ntiles, 1), kMaxGrid));
+  const u64 inv = invert ? ~0ull : 0ull;
+  switch (mode) {
+    case kWrite:
+      launch_mode<kWrite>(pat, grid, s, p, n, base, seed, inv, rep, cap);
+      break;
+    case kVerify:
+      launch_mode<kVerify>(pat, grid, s, p, n, base, seed, inv, rep, cap);
+      break;
+    case kVerifyFlip:
+      launch_mode<kVerifyFlip>(pat, grid, s, p, n, base, seed, inv, rep, cap);
+      break;
+    default:
+      TORCH_CHECK(false, "unknown memtest mode ", mode);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+int parse_pattern(const std::string& name) {
+  if (name == "addr") return kAddr;
+  if (name == "rand") return kRand;
+  if (name == "zero") return kZero;
+  TORCH_CHECK(false, "memtest pattern must be 'addr', 'rand' or 'zero', got '",
+              name, "'");
+  return -1;
+}
+
+u64 check_max_records(long long max_records) {
+  TORCH_CHECK(max_records >= 0 && (u64)max_records <= kMaxRecordsLimit,
+              "max_records must be in [0, ", kMaxRecordsLimit, "]");
+  return (u64)max_records;
+}
+
+// ---------------------------------------------------------------------------
+// Tensor bindings: the numerics-testable surface
+// ---------------------------------------------------------------------------
+
+void check_tensor(const torch::Tensor& t) {
+  TORCH_CHECK(t.is_cuda(), "memtest: tensor must be on the GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kInt64, "memtest: int64 only");
+  TORCH_CHECK(t.dim() == 1 && t.is_contiguous(),
+              "memtest: 1-D contiguous tensor required");
+  int cur = -1;
+  HIP_CHECK(hipGetDevice(&cur));
+  TORCH_CHECK(t.get_device() == cur, "memtest: tensor is on device ",
+              t.get_device(), " but the current device is ", cur);
+}
+
+void memtest_write(torch::Tensor t, const std::string& pattern, u64 seed,
+                   u64 base_word, bool invert) {
+  check_tensor(t);
+  int pat = parse_pattern(pattern);
+  auto stream = at::hip::getCurrentHIPStream();
+  launch(kWrite, pat, reinterpret_cast<u64*>(t.data_ptr<int64_t>()),
+         (u64)t.numel(), base_word, seed, invert, nullptr, 0, stream.stream());
+}
+
+py::dict report_dict(const u64* h, u64 cap) {
+  py::dict d;
+  d["errors"] = py::int_(h[kRepErrors]);
+  d["bad_bits"] = py::int_(h[kRepBits]);
+  py::list recs;
+  u64 nrec = std::min<u64>(h[kRepClaimed], cap);
+  for (u64 i = 0; i < nrec; ++i) {
+    const u64* r = h + kRepHeader + 3 * i;
+    recs.append(py::make_tuple(py::int_(r[0]), py::int_(r[1]), py::int_(r[2])));
+  }
+  d["records"] = recs;
+  return d;
+}
+
+py::dict verify_tensor(int mode, torch::Tensor t, const std::string& pattern,
+                       u64 seed, u64 base_word, bool invert,
+                       long long max_records) {
+  check_tensor(t);
+  int pat = parse_pattern(pattern);
+  u64 cap = check_max_records(max_records);
+  auto rep = torch::zeros({(int64_t)(kRepHeader + 3 * cap)}, t.options());
+  auto stream = at::hip::getCurrentHIPStream();
+  launch(mode, pat, reinterpret_cast<u64*>(t.data_ptr<int64_t>()),
+         (u64)t.numel(), base_word, seed, invert,
+         reinterpret_cast<u64*>(rep.data_ptr<int64_t>()), cap, stream.stream());
+  auto host = rep.cpu();  // synchronises with the current stream
+  return report_dict(reinterpret_cast<const u64*>(host.data_ptr<int64_t>()),
+                     cap);
+}
+
+py::dict memtest_verify(torch::Tensor t, const std::string& pattern, u64 seed,
+                        u64 base_word, bool invert, long long max_records) {
+  return verify_tensor(kVerify, t, pattern, seed, base_word, invert,
+                       max_records);
+}
+
+py::dict memtest_verify_flip(torch::Tensor t, const std::string& pattern,
+                             u64 seed, u64 base_word, bool invert,
+                             long long max_records) {
+  return verify_tensor(kVerifyFlip, t, pattern, seed, base_word, invert,
+                       max_records);
+}
+
+py::dict memtest_geometry() {
+  py::dict d;
+  d["block"] = kBlock;
+  d["words_per_thread_iter"] = kWordsPerThreadIter;
+  d["max_grid"] = kMaxGrid;
+  return d;
+}
+
+// ---------------------------------------------------------------------------
+// Driver: the burn-in pass over hipMalloc'd chunks
+// ---------------------------------------------------------------------------
+
+struct DevMem {
+  void* ptr = nullptr;
+  DevMem() = default;
+  DevMem(const DevMem&) = delete;
+  DevMem& operator=(const DevMem&) = delete;
+  DevMem(DevMem&& o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
+  ~DevMem() {
+    if (ptr) (void)hipFree(ptr);
+  }
+};
+
+struct StreamGuard {
+  hipStream_t s = nullptr;
+  ~StreamGuard() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+struct EventGuard {
+  hipEvent_t e = nullptr;
+  ~EventGuard() {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// Restores the caller's current device (torch keeps its own notion of it).
+struct DeviceRestore {
+  int prev = -1;
+  ~DeviceRestore() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+struct StepRecord {
+  const char* step;
+  u64 g, expected, actual;
+};
+
+struct DriverResult {
+  u64 bytes = 0, errors = 0, bad_bits = 0;
+  int passes = 0;
+  double write_ms = 0, verify_ms = 0, seconds = 0;
+  std::vector<StepRecord> records;
+};
+
+DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
+                        u64 seed, u64 cap, bool scrub,
+                        const std::vector<std::pair<u64, u64>>& inject) {
+  DriverResult out;
+  u64 total_words = 0;
+  for (u64 w : chunk_words) total_words += w;
+  out.bytes = total_words * 8;
+  for (auto& in : inject)
+    TORCH_CHECK(in.first < total_words, "inject: word ", in.first,
+                " is outside the ", total_words, " words under test");
+
+  DeviceRestore restore;
+  HIP_CHECK(hipGetDevice(&restore.prev));
+  HIP_CHECK(hipSetDevice(device));
+
+  std::vector<DevMem> chunks(chunk_words.size());
+  for (size_t i = 0; i < chunk_words.size(); ++i)
+    HIP_CHECK(hipMalloc(&chunks[i].ptr, chunk_words[i] * 8));
+  const size_t rep_words = kRepHeader + 3 * cap;
+  DevMem rep;
+  HIP_CHECK(hipMalloc(&rep.ptr, rep_words * 8));
+  std::vector<u64> host_rep(rep_words);
+
+  StreamGuard stream;
+  HIP_CHECK(hipStreamCreate(&stream.s));
+  EventGuard t0, t1, w0, w1;
+  HIP_CHECK(hipEventCreate(&t0.e));
+  HIP_CHECK(hipEventCreate(&t1.e));
+  HIP_CHECK(hipEventCreate(&w0.e));
+  HIP_CHECK(hipEventCreate(&w1.e));
+  HIP_CHECK(hipEventRecord(w0.e, stream.s));
+
+  // One step = one mode over ALL chunks: with >= 1 GiB under test every line
+  // has left the 256 MiB Infinity Cache before the next step reads it, so
+  // the read-back comes from HBM.
+  auto step = [&](const char* name, int mode, int pat, bool invert) {
+    if (mode != kWrite)
+      HIP_CHECK(hipMemsetAsync(rep.ptr, 0, rep_words * 8, stream.s));
+    HIP_CHECK(hipEventRecord(t0.e, stream.s));
+    u64 g = 0;
+    for (size_t i = 0; i < chunks.size(); ++i) {
+      launch(mode, pat, static_cast<u64*>(chunks[i].ptr), chunk_words[i], g,
+             seed, invert, static_cast<u64*>(rep.ptr), cap, stream.s);
+      g += chunk_words[i];
+    }
+    HIP_CHECK(hipEventRecord(t1.e, stream.s));
+    if (mode != kWrite)
+      HIP_CHECK(hipMemcpyAsync(host_rep.data(), rep.ptr, rep_words * 8,
+                               hipMemcpyDeviceToHost, stream.s));
+    HIP_CHECK(hipStreamSynchronize(stream.s));
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
+    ++out.passes;
+    if (mode == kWrite) {
+      if (pat != kZero) out.write_ms += ms;
+      return;
+    }
+    out.verify_ms += ms;
+    out.errors += host_rep[kRepErrors];
+    out.bad_bits |= host_rep[kRepBits];
+    u64 nrec = std::min<u64>(host_rep[kRepClaimed], cap);
+    for (u64 i = 0; i < nrec && out.records.size() < cap; ++i) {
+      const u64* r = host_rep.data() + kRepHeader + 3 * i;
+      out.records.push_back({name, r[0], r[1], r[2]});
+    }
+  };
+
+  step("write addr", kWrite, kAddr, false);
+  // detector self-test: flip bits behind the kernel's back
+  for (auto& in : inject) {
+    u64 g = in.first, off = 0;
+    size_t c = 0;
+    while (g - off >= chunk_words[c]) off += chunk_words[c++];
+    u64* addr = static_cast<u64*>(chunks[c].ptr) + (g - off);
+    u64 word = 0;
+    HIP_CHECK(hipMemcpy(&word, addr, 8, hipMemcpyDeviceToHost));
+    word ^= in.second;
+    HIP_CHECK(hipMemcpy(addr, &word, 8, hipMemcpyHostToDevice));
+  }
+  step("verify addr", kVerify, kAddr, false);
+  step("write rand", kWrite, kRand, false);
+  step("verify rand", kVerify, kRand, false);
+  step("verify_flip rand", kVerifyFlip, kRand, false);
+  step("verify rand inverted", kVerify, kRand, true);
+  if (scrub) step("scrub", kWrite, kZero, false);
+
+  HIP_CHECK(hipEventRecord(w1.e, stream.s));
+  HIP_CHECK(hipEventSynchronize(w1.e));
+  float wall = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&wall, w0.e, w1.e));
+  out.seconds = wall / 1e3;
+  return out;
+}
+
+py::dict hbm_memtest(int device, std::vector<u64> chunk_bytes, u64 seed,
+                     long long max_records, bool scrub,
+                     std::vector<std::pair<u64, u64>> inject) {
+  u64 cap = check_max_records(max_records);
+  int ndev = 0;
+  HIP_CHECK(hipGetDeviceCount(&ndev));
+  TORCH_CHECK(device >= 0 && device < ndev, "no such device ", device);
+  TORCH_CHECK(!chunk_bytes.empty(), "chunk_bytes must not be empty");
+  std::vector<u64> words;
+  for (u64 b : chunk_bytes) {
+    TORCH_CHECK(b > 0 && b % 8 == 0,
+                "every chunk must be a positive multiple of 8 bytes, got ", b);
+    words.push_back(b / 8);
+  }
+  DriverResult r;
+  {
+    py::gil_scoped_release release;
+    r = run_driver(device, words, seed, cap, scrub, inject);
+  }
+  py::dict d;
+  d["bytes_tested"] = py::int_(r.bytes);
+  d["passes"] = r.passes;
+  d["errors"] = py::int_(r.errors);
+  d["bad_bits"] = py::int_(r.bad_bits);
+  py::list recs;
+  for (auto& rec : r.records) {
+    py::dict e;
+    e["step"] = std::string(rec.step);
+    e["g"] = py::int_(rec.g);
+    e["expected"] = py::int_(rec.expected);
+    e["actual"] = py::int_(rec.actual);
+    recs.append(e);
+  }
+  d["records"] = recs;
+  // bytes counted once per pass: 2 timed write steps, 4 timed verify steps
+  d["write_gbps"] = r.write_ms > 0 ? 2.0 * r.bytes / (r.write_ms * 1e6) : 0.0;
+  d["verify_gbps"] = r.verify_ms > 0 ? 4.0 * r.bytes / (r.verify_ms * 1e6) : 0.0;
+  d["seconds"] = r.seconds;
+  return d;
+}
+
+}  // namespace hbm_memtest

@@ -7,6 +7,8 @@
 //   * xGMI / HBM bandwidth probe kernels: vectorized float4 grid-stride
 //     copy, local (HBM stream) and peer-to-peer (pull over xGMI). Feeds the
 //     scheduler's adjacency matrix (parallel/topology.py).
+//   * HBM pattern memory test (hbm_memtest.hip): write / verify / verify_flip
+//     over seeded 64-bit words — the burn-in's data-integrity pass.
 //   * MFMA warm-up / validation tiles: the exact-f32 16x16x4 MFMA (operand
 //     maps documented in the CDNA4 guide) and the bf16 16x16x32 MFMA —
 //     clock ramp before measuring, numerics check against torch fp32.
@@ -189,6 +191,7 @@ __global__ void mfma_warmup_kernel(float* __restrict__ sink, int iters) {
 #include "gemm_bf16.hip"
 #include "gemm_bf16_8phase.hip"
 #include "gemm_fp8_mx.hip"
+#include "hbm_memtest.hip"
 
 namespace {
 
@@ -1009,4 +1012,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("p2p_matrix", &p2p_matrix, py::arg("mib") = 256, py::arg("iters") = 5,
         py::call_guard<py::gil_scoped_release>());
+  m.def("memtest_write", &hbm_memtest::memtest_write, py::arg("t"),
+        py::arg("pattern"), py::arg("seed"), py::arg("base_word") = 0,
+        py::arg("invert") = false);
+  m.def("memtest_verify", &hbm_memtest::memtest_verify, py::arg("t"),
+        py::arg("pattern"), py::arg("seed"), py::arg("base_word") = 0,
+        py::arg("invert") = false, py::arg("max_records") = 32);
+  m.def("memtest_verify_flip", &hbm_memtest::memtest_verify_flip, py::arg("t"),
+        py::arg("pattern"), py::arg("seed"), py::arg("base_word") = 0,
+        py::arg("invert") = false, py::arg("max_records") = 32);
+  m.def("memtest_geometry", &hbm_memtest::memtest_geometry);
+  m.def("hbm_memtest", &hbm_memtest::hbm_memtest, py::arg("device"),
+        py::arg("chunk_bytes"), py::arg("seed"), py::arg("max_records") = 32,
+        py::arg("scrub") = false,
+        py::arg("inject") =
+            std::vector<std::pair<unsigned long long, unsigned long long>>{});
 }

@@ -248,13 +248,20 @@ def res_ports():
 def res_validate(
     size: int = typer.Option(4096, "--size"),
     iters: int = typer.Option(5, "--iters"),
+    memtest_mib: int = typer.Option(
+        0, "--memtest-mib", help="also pattern-test this many MiB of HBM per GPU (0 = off)"
+    ),
 ):
-    """Burn-in free GPUs (HBM bandwidth + bf16/MX-fp8/MX-fp4 MFMA TFLOPS)."""
+    """Burn-in free GPUs (HBM bandwidth + bf16/MX-fp8/MX-fp4 MFMA TFLOPS,
+    optionally an HBM pattern memory test)."""
+    body = {"size": size, "iters": iters}
+    if memtest_mib:
+        body["memtestMiB"] = memtest_mib
     with _client() as c:
         _show(
             c.post(
                 "/api/v1/resources/gpus/validate",
-                json={"size": size, "iters": iters},
+                json=body,
                 timeout=600,
             )
         )

@@ -88,15 +88,65 @@ async def run_probe_async(mib: int = 256, iters: int = 5) -> dict:
     )
 
 
+MEMTEST_SEED = 0x0123456789ABCDEF
+_GIB = 1 << 30
+
+
+def memtest_plan(
+    free_bytes: int, want_bytes: int, chunk_bytes: int = 1 << 30, reserve_bytes: int = 2 << 30
+) -> list:
+    """Chunk sizes for an HBM pattern test: min(want, free - reserve) rounded
+    down to a multiple of 16, cut into chunk_bytes pieces with one short last
+    chunk. Empty when less than 1 GiB would remain: every step covers all
+    chunks before the next one starts, and below that the read-back could be
+    served from the 256 MiB Infinity Cache instead of HBM."""
+    total = (min(int(want_bytes), int(free_bytes) - int(reserve_bytes)) // 16) * 16
+    if total < _GIB:
+        return []
+    chunk = max(16, (int(chunk_bytes) // 16) * 16)
+    plan = [chunk] * (total // chunk)
+    if total % chunk:
+        plan.append(total % chunk)
+    return plan
+
+
+def memtest_gpu(
+    index: int,
+    mib: int = 4096,
+    seed: int = MEMTEST_SEED,
+    scrub: bool = False,
+    inject: Optional[list] = None,
+) -> dict:
+    """HBM data-integrity pass over `mib` MiB of GPU `index` (address and
+    pseudorandom patterns, written, read back, complemented and read back
+    again; csrc/hbm_memtest.hip). The plan comes from the free HBM hipMemGetInfo
+    reports, less a reserve for the runtime."""
+    ext = load_ext()
+    free = int(ext.device_info(index)["freeMem"])
+    plan = memtest_plan(free, int(mib) << 20)
+    if not plan:
+        return {"skipped": "insufficient free HBM"}
+    report = ext.hbm_memtest(index, plan, seed, 32, scrub, list(inject or []))
+    for key, digits in (("write_gbps", 1), ("verify_gbps", 1), ("seconds", 4)):
+        if key in report:
+            report[key] = round(report[key], digits)
+    return report
+
+
 def validate_gpus(
-    indices: Optional[list] = None, size: int = 4096, iters: int = 5, fp8: bool = True
+    indices: Optional[list] = None,
+    size: int = 4096,
+    iters: int = 5,
+    fp8: bool = True,
+    memtest_mib: int = 0,
 ) -> dict:
     """Per-GPU health burn-in: HBM stream bandwidth + dense bf16 MFMA GEMM
     (the 8-phase 256^2 structure, ~1.1 PF) + the MX-fp8 path (block-scaled
     mfma_scale 16x16x128, ~1.9 PF — exercised because fp8 training is what
     tenants run on MI355X and its datapath can fail independently of bf16).
     Run on FREE GPUs before scheduling; a GPU far below its siblings is
-    flagged."""
+    flagged. With memtest_mib > 0 each GPU also gets the HBM pattern test
+    (memtest_gpu) and is unhealthy if a single word read back wrong."""
     ext = load_ext()
     n = ext.device_count()
     idx = list(indices) if indices else list(range(n))
@@ -121,18 +171,24 @@ def validate_gpus(
             entry["fp8_tflops"] = round(ext.gemm_fp8_mx_tflops(i, size, iters), 1)
         if fp8 and size % 256 == 0 and size >= 512:
             entry["fp4_tflops"] = round(ext.gemm_fp4_mx_tflops(i, size, iters), 1)
+        if memtest_mib > 0:
+            entry["memtest"] = memtest_gpu(i, memtest_mib)
         report["gpus"].append(entry)
     vals = [g["bf16_tflops"] for g in report["gpus"]]
     if vals:
         top = max(vals)
         for g in report["gpus"]:
             g["healthy"] = bool(g["bf16_tflops"] > 0.7 * top and g["hbm_gbps"] > 2000)
+            if "memtest" in g and "errors" in g["memtest"]:
+                g["healthy"] = bool(g["healthy"] and g["memtest"]["errors"] == 0)
     return report
 
 
-async def validate_gpus_async(indices: Optional[list] = None, size: int = 4096, iters: int = 5) -> dict:
+async def validate_gpus_async(
+    indices: Optional[list] = None, size: int = 4096, iters: int = 5, memtest_mib: int = 0
+) -> dict:
     return await asyncio.get_running_loop().run_in_executor(
-        None, lambda: validate_gpus(indices, size, iters)
+        None, lambda: validate_gpus(indices, size, iters, memtest_mib=memtest_mib)
     )
 
 

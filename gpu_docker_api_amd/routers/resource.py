@@ -25,8 +25,9 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
     @r.post("/gpus/validate")
     async def gpus_validate(request: Request):
         """MI355X extension: burn-in the node's FREE GPUs (HBM bandwidth +
-        dense bf16 MFMA GEMM) before trusting them with placements. Busy
-        GPUs are skipped unless explicitly listed."""
+        dense bf16 MFMA GEMM, and with `memtestMiB` an HBM pattern memory
+        test) before trusting them with placements. Busy GPUs are skipped
+        unless explicitly listed."""
         try:
             body = await request.json()
         except Exception:
@@ -51,6 +52,9 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
         try:
             size = int(body.get("size", 4096))
             iters = int(body.get("iters", 5))
+            memtest = body.get("memtestMiB", 0)
+            if isinstance(memtest, bool) or not isinstance(memtest, int):
+                raise TypeError("memtestMiB must be an int")
         except (TypeError, ValueError):
             from .codes import Code
             from .response import error
@@ -59,8 +63,14 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
         try:
             from ..ops import hipcore
 
+            # HBM pattern test: off at 0, else 1 GiB .. the whole 288 GB card
+            if memtest != 0:
+                memtest = max(1024, min(memtest, 294912))
             report = await hipcore.validate_gpus_async(
-                idx, max(256, min(size, 16384)), max(1, min(iters, 50))
+                idx,
+                max(256, min(size, 16384)),
+                max(1, min(iters, 50)),
+                memtest_mib=memtest,
             )
         except Exception as exc:  # noqa: BLE001 — no GPU / extension absent
             from .codes import Code
