@@ -1,505 +1,24 @@
-// Native bulk copy engine: io_uring small-file batching + in-kernel
-// copy_file_range for large files (raw syscalls — liburing is not present).
-//
-// Replaces the reference's two data movers (SURVEY.md §2.4 row "Data
-// migration"): the shell tar pipe for the container writable layer
-// (/root/reference/utils/copy.go:17-27) and the throwaway-ubuntu-container
-// `mv` for volumes (utils/copy.go:74-128). Design, from measuring a
-// rootfs-shaped tree (thousands of 4 KiB files + a few GiB of large files):
-//
-//   * LARGE files are copied with extent-aware copy_file_range — fully
-//     in-kernel (reflink/server-side copy capable), no user-space bounce;
-//     holes found via SEEK_DATA/SEEK_HOLE are never touched.
-//   * SMALL files (<= 256 KiB) dominate syscall count, not bytes: they are
-//     batched through ONE io_uring — up to 16 files in flight, each a single
-//     READ then WRITE — amortizing ring submissions across files.
-//   * metadata preserved everywhere: mode/uid/gid/mtime, symlinks, hardlinks
-//     (within one call), device nodes (overlayfs whiteouts are 0:0 char
-//     devices), xattrs (overlayfs opaque markers).
-//   * graceful fallback at every level: no io_uring (seccomp/EPERM) ->
-//     copy_file_range loop; no copy_file_range (EXDEV on old kernels) ->
-//     pread/pwrite.
-//
-// Exposed to Python as gpu_docker_api_amd.ops._iocopy (pybind11).
+// pybind11 binding of csrc/iocopy_core.h: the bulk copy engine (io_uring
+// small-file batching + copy_file_range), exposed to Python as
+// gpu_docker_api_amd.ops._iocopy. Everything but the binding lives in the
+// header, which csrc/iocopy_selftest.cpp drives stand-alone.
 #include <pybind11/pybind11.h>
 
-#include <atomic>
-#include <cerrno>
-#include <climits>
-#include <cstring>
-#include <map>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
-#include <dirent.h>
-#include <fcntl.h>
-#include <linux/io_uring.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <sys/syscall.h>
-#include <sys/types.h>
-#include <sys/xattr.h>
-#include <unistd.h>
+#include "iocopy_core.h"
 
 namespace py = pybind11;
 
 namespace {
 
-[[noreturn]] void die(const std::string& what) {
-  throw std::runtime_error(what + ": " + std::strerror(errno));
-}
-
-constexpr size_t kChunk = 1 << 20;           // 1 MiB large-file bounce chunk
-constexpr unsigned kDepth = 16;              // files in flight in the ring
-constexpr size_t kSmallCutoff = 256 * 1024;  // <= this: batched via io_uring
-
-// ---------------------------------------------------------------------------
-// Minimal io_uring wrapper (setup/enter via raw syscalls)
-// ---------------------------------------------------------------------------
-
-int sys_io_uring_setup(unsigned entries, struct io_uring_params* p) {
-  return (int)syscall(__NR_io_uring_setup, entries, p);
-}
-int sys_io_uring_enter(int fd, unsigned to_submit, unsigned min_complete,
-                       unsigned flags) {
-  return (int)syscall(__NR_io_uring_enter, fd, to_submit, min_complete, flags,
-                      nullptr, 0);
-}
-
-class Ring {
- public:
-  static constexpr unsigned kEntries = 64;
-
-  bool init() {
-    std::memset(&params_, 0, sizeof(params_));
-    fd_ = sys_io_uring_setup(kEntries, &params_);
-    if (fd_ < 0) return false;
-
-    sring_sz_ = params_.sq_off.array + params_.sq_entries * sizeof(unsigned);
-    cring_sz_ = params_.cq_off.cqes + params_.cq_entries * sizeof(io_uring_cqe);
-    bool single_mmap = params_.features & IORING_FEAT_SINGLE_MMAP;
-    if (single_mmap && cring_sz_ > sring_sz_) sring_sz_ = cring_sz_;
-
-    sq_ptr_ = mmap(nullptr, sring_sz_, PROT_READ | PROT_WRITE,
-                   MAP_SHARED | MAP_POPULATE, fd_, IORING_OFF_SQ_RING);
-    if (sq_ptr_ == MAP_FAILED) return false;
-    cq_ptr_ = single_mmap
-                  ? sq_ptr_
-                  : mmap(nullptr, cring_sz_, PROT_READ | PROT_WRITE,
-                         MAP_SHARED | MAP_POPULATE, fd_, IORING_OFF_CQ_RING);
-    if (cq_ptr_ == MAP_FAILED) return false;
-    sqes_sz_ = params_.sq_entries * sizeof(io_uring_sqe);
-    sqes_ = (io_uring_sqe*)mmap(nullptr, sqes_sz_,
-                                PROT_READ | PROT_WRITE, MAP_SHARED | MAP_POPULATE,
-                                fd_, IORING_OFF_SQES);
-    if (sqes_ == MAP_FAILED) return false;
-
-    auto* sq = (char*)sq_ptr_;
-    sq_tail_ = (std::atomic<unsigned>*)(sq + params_.sq_off.tail);
-    sq_mask_ = *(unsigned*)(sq + params_.sq_off.ring_mask);
-    sq_array_ = (unsigned*)(sq + params_.sq_off.array);
-    auto* cq = (char*)cq_ptr_;
-    cq_head_ = (std::atomic<unsigned>*)(cq + params_.cq_off.head);
-    cq_tail_ = (std::atomic<unsigned>*)(cq + params_.cq_off.tail);
-    cq_mask_ = *(unsigned*)(cq + params_.cq_off.ring_mask);
-    cqes_ = (io_uring_cqe*)(cq + params_.cq_off.cqes);
-    ok_ = true;
-    return true;
-  }
-
-  bool ok() const { return ok_; }
-
-  void queue(unsigned op, int fd, void* buf, unsigned len, off_t off,
-             unsigned long long user_data) {
-    unsigned tail = sq_tail_->load(std::memory_order_relaxed);
-    unsigned idx = tail & sq_mask_;
-    io_uring_sqe* sqe = &sqes_[idx];
-    std::memset(sqe, 0, sizeof(*sqe));
-    sqe->opcode = op;
-    sqe->fd = fd;
-    sqe->addr = (unsigned long long)buf;
-    sqe->len = len;
-    sqe->off = (unsigned long long)off;
-    sqe->user_data = user_data;
-    sq_array_[idx] = idx;
-    sq_tail_->store(tail + 1, std::memory_order_release);
-    ++pending_submit_;
-  }
-
-  void submit(unsigned wait) {
-    int ret = sys_io_uring_enter(fd_, pending_submit_, wait,
-                                 wait ? IORING_ENTER_GETEVENTS : 0);
-    if (ret < 0) die("io_uring_enter");
-    pending_submit_ = 0;
-  }
-
-  bool pop(unsigned long long* user_data, int* res) {
-    unsigned head = cq_head_->load(std::memory_order_relaxed);
-    if (head == cq_tail_->load(std::memory_order_acquire)) return false;
-    io_uring_cqe* cqe = &cqes_[head & cq_mask_];
-    *user_data = cqe->user_data;
-    *res = cqe->res;
-    cq_head_->store(head + 1, std::memory_order_release);
-    return true;
-  }
-
-  void wait_one() { submit(1); }
-
-  ~Ring() {
-    // closing the fd does NOT unmap the rings — without these munmaps a
-    // long-lived daemon leaks ~2 pages per copy_tree call (found as ~8.6
-    // KB/cycle RSS creep in a 15-minute churn soak)
-    if (sqes_ != nullptr && sqes_ != MAP_FAILED) munmap(sqes_, sqes_sz_);
-    if (cq_ptr_ != nullptr && cq_ptr_ != MAP_FAILED && cq_ptr_ != sq_ptr_)
-      munmap(cq_ptr_, cring_sz_);
-    if (sq_ptr_ != nullptr && sq_ptr_ != MAP_FAILED) munmap(sq_ptr_, sring_sz_);
-    if (fd_ >= 0) close(fd_);
-  }
-
- private:
-  int fd_ = -1;
-  bool ok_ = false;
-  io_uring_params params_{};
-  void* sq_ptr_ = nullptr;
-  void* cq_ptr_ = nullptr;
-  size_t sring_sz_ = 0;
-  size_t cring_sz_ = 0;
-  size_t sqes_sz_ = 0;
-  io_uring_sqe* sqes_ = nullptr;
-  std::atomic<unsigned>* sq_tail_ = nullptr;
-  unsigned sq_mask_ = 0;
-  unsigned* sq_array_ = nullptr;
-  std::atomic<unsigned>* cq_head_ = nullptr;
-  std::atomic<unsigned>* cq_tail_ = nullptr;
-  unsigned cq_mask_ = 0;
-  io_uring_cqe* cqes_ = nullptr;
-  unsigned pending_submit_ = 0;
-};
-
-// ---------------------------------------------------------------------------
-// Metadata
-// ---------------------------------------------------------------------------
-
-void copy_xattrs(const std::string& src, const std::string& dst) {
-  ssize_t list_sz = llistxattr(src.c_str(), nullptr, 0);
-  if (list_sz <= 0) return;
-  std::vector<char> names(list_sz);
-  list_sz = llistxattr(src.c_str(), names.data(), names.size());
-  if (list_sz <= 0) return;
-  std::vector<char> value;
-  for (char* p = names.data(); p < names.data() + list_sz;) {
-    std::string name(p);
-    p += name.size() + 1;
-    ssize_t vs = lgetxattr(src.c_str(), name.c_str(), nullptr, 0);
-    if (vs < 0) continue;
-    value.resize(vs);
-    vs = lgetxattr(src.c_str(), name.c_str(), value.data(), value.size());
-    if (vs < 0) continue;
-    // best-effort: security.* may need privileges we lack
-    (void)lsetxattr(dst.c_str(), name.c_str(), value.data(), vs, 0);
-  }
-}
-
-void copy_meta(const std::string& dst, const struct stat& st) {
-  int rc = lchown(dst.c_str(), st.st_uid, st.st_gid);
-  (void)rc;
-  if (!S_ISLNK(st.st_mode)) (void)chmod(dst.c_str(), st.st_mode & 07777);
-  struct timespec times[2] = {st.st_atim, st.st_mtim};
-  (void)utimensat(AT_FDCWD, dst.c_str(), times, AT_SYMLINK_NOFOLLOW);
-}
-
-// ---------------------------------------------------------------------------
-// Large-file copy: extent-aware, in-kernel
-// ---------------------------------------------------------------------------
-
-std::vector<std::pair<off_t, off_t>> data_extents(int fd, off_t size) {
-  std::vector<std::pair<off_t, off_t>> out;
-  off_t pos = 0;
-  while (pos < size) {
-    off_t data = lseek(fd, pos, SEEK_DATA);
-    if (data < 0) {
-      if (errno == ENXIO) break;          // trailing hole
-      out.push_back({pos, size});         // SEEK_DATA unsupported: whole file
-      break;
-    }
-    off_t hole = lseek(fd, data, SEEK_HOLE);
-    if (hole < 0) hole = size;
-    out.push_back({data, hole});
-    pos = hole;
-  }
-  return out;
-}
-
-void copy_data_large(int in_fd, int out_fd, off_t size) {
-  auto extents = data_extents(in_fd, size);
-  if (ftruncate(out_fd, size) != 0) die("ftruncate");
-  std::vector<char> buf;
-  for (auto [start, end] : extents) {
-    off_t off = start;
-    while (off < end) {
-      size_t want = (size_t)std::min<off_t>((off_t)(8 * kChunk), end - off);
-      off_t off_out = off;
-      ssize_t n = copy_file_range(in_fd, &off, out_fd, &off_out, want, 0);
-      if (n > 0) continue;  // both offsets advanced by the kernel
-      // EXDEV / unsupported: plain pread/pwrite with explicit offsets
-      if (buf.empty()) buf.resize(kChunk);
-      ssize_t r = pread(in_fd, buf.data(), std::min(want, kChunk), off);
-      if (r < 0) die("pread");
-      if (r == 0) break;
-      ssize_t w = 0;
-      while (w < r) {
-        ssize_t k = pwrite(out_fd, buf.data() + w, r - w, off + w);
-        if (k < 0) die("pwrite");
-        w += k;
-      }
-      off += r;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Small-file copy: batched across files through one io_uring
-// ---------------------------------------------------------------------------
-
-struct FileJob {
-  std::string src, dst;
-  struct stat st;
-};
-
-struct Slot {
-  std::vector<char> buf;
-  int in_fd = -1, out_fd = -1;
-  size_t len = 0;
-  size_t job_idx = 0;
-  bool reading = false;
-};
-
-struct CopyStats {
-  unsigned long long files = 0, dirs = 0, symlinks = 0, specials = 0;
-  unsigned long long bytes = 0;
-  bool used_uring = false;
-};
-
-void finish_small(const FileJob& job) {
-  copy_xattrs(job.src, job.dst);
-  copy_meta(job.dst, job.st);
-}
-
-void copy_small_fallback(const FileJob& job) {
-  int in_fd = open(job.src.c_str(), O_RDONLY | O_CLOEXEC);
-  if (in_fd < 0) die("open " + job.src);
-  int out_fd = open(job.dst.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0600);
-  if (out_fd < 0) {
-    close(in_fd);
-    die("open " + job.dst);
-  }
-  copy_data_large(in_fd, out_fd, job.st.st_size);
-  close(in_fd);
-  close(out_fd);
-  finish_small(job);
-}
-
-void copy_small_batch(Ring& ring, const std::vector<FileJob>& jobs,
-                      CopyStats& stats) {
-  if (!ring.ok()) {
-    for (const auto& j : jobs) copy_small_fallback(j);
-    return;
-  }
-  stats.used_uring = !jobs.empty();
-  std::vector<Slot> slots(kDepth);
-  for (auto& s : slots) s.buf.resize(kSmallCutoff);
-  std::vector<unsigned> free_slots;
-  for (unsigned i = 0; i < kDepth; ++i) free_slots.push_back(i);
-
-  size_t next_job = 0;
-  unsigned in_flight = 0;
-
-  auto start_next = [&]() -> bool {
-    if (next_job >= jobs.size() || free_slots.empty()) return false;
-    const FileJob& job = jobs[next_job];
-    unsigned si = free_slots.back();
-    Slot& s = slots[si];
-    s.in_fd = open(job.src.c_str(), O_RDONLY | O_CLOEXEC);
-    if (s.in_fd < 0) die("open " + job.src);
-    s.out_fd = open(job.dst.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0600);
-    if (s.out_fd < 0) {
-      close(s.in_fd);
-      die("open " + job.dst);
-    }
-    free_slots.pop_back();
-    s.job_idx = next_job++;
-    s.len = (size_t)jobs[s.job_idx].st.st_size;
-    s.reading = true;
-    ring.queue(IORING_OP_READ, s.in_fd, s.buf.data(), (unsigned)s.len, 0, si);
-    ++in_flight;
-    return true;
-  };
-
-  while (start_next()) {
-  }
-  ring.submit(0);
-
-  while (in_flight > 0) {
-    unsigned long long ud;
-    int res;
-    if (!ring.pop(&ud, &res)) {
-      ring.wait_one();
-      continue;
-    }
-    --in_flight;
-    Slot& s = slots[ud];
-    if (res < 0) {
-      errno = -res;
-      die(s.reading ? "io_uring read" : "io_uring write");
-    }
-    if (s.reading) {
-      s.len = (size_t)res;  // actual bytes read
-      s.reading = false;
-      ring.queue(IORING_OP_WRITE, s.out_fd, s.buf.data(), (unsigned)s.len, 0, ud);
-      ++in_flight;
-      ring.submit(0);
-    } else {
-      close(s.in_fd);
-      close(s.out_fd);
-      finish_small(jobs[s.job_idx]);
-      free_slots.push_back((unsigned)ud);
-      bool queued = false;
-      while (start_next()) queued = true;
-      if (queued) ring.submit(0);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Tree walk
-// ---------------------------------------------------------------------------
-
-struct Walker {
-  Ring& ring;
-  std::map<std::pair<dev_t, ino_t>, std::string> hardlinks;
-  std::vector<FileJob> small;
-  std::vector<std::pair<std::string, struct stat>> dir_meta;
-  CopyStats stats;
-
-  explicit Walker(Ring& r) : ring(r) {}
-
-  void walk(const std::string& src, const std::string& dst) {
-    struct stat st;
-    if (lstat(src.c_str(), &st) != 0) die("lstat " + src);
-
-    if (S_ISDIR(st.st_mode)) {
-      if (mkdir(dst.c_str(), st.st_mode & 07777) != 0 && errno != EEXIST)
-        die("mkdir " + dst);
-      ++stats.dirs;
-      DIR* d = opendir(src.c_str());
-      if (!d) die("opendir " + src);
-      while (dirent* e = readdir(d)) {
-        std::string n(e->d_name);
-        if (n == "." || n == "..") continue;
-        walk(src + "/" + n, dst + "/" + n);
-      }
-      closedir(d);
-      copy_xattrs(src, dst);
-      dir_meta.push_back({dst, st});  // applied last (mtime survives fills)
-      return;
-    }
-
-    if (S_ISLNK(st.st_mode)) {
-      std::vector<char> target(st.st_size ? st.st_size + 1 : PATH_MAX);
-      ssize_t n = readlink(src.c_str(), target.data(), target.size() - 1);
-      if (n < 0) die("readlink " + src);
-      target[n] = 0;
-      (void)unlink(dst.c_str());
-      if (symlink(target.data(), dst.c_str()) != 0) die("symlink " + dst);
-      copy_meta(dst, st);
-      ++stats.symlinks;
-      return;
-    }
-
-    if (S_ISCHR(st.st_mode) || S_ISBLK(st.st_mode) || S_ISFIFO(st.st_mode) ||
-        S_ISSOCK(st.st_mode)) {
-      // overlayfs whiteouts are 0:0 char devices — must be replicated
-      (void)unlink(dst.c_str());
-      if (mknod(dst.c_str(), st.st_mode, st.st_rdev) != 0) {
-        ++stats.specials;  // unprivileged: cannot mknod; skip
-        return;
-      }
-      copy_xattrs(src, dst);
-      copy_meta(dst, st);
-      ++stats.specials;
-      return;
-    }
-
-    // regular file
-    auto key = std::make_pair(st.st_dev, st.st_ino);
-    if (st.st_nlink > 1) {
-      auto it = hardlinks.find(key);
-      if (it != hardlinks.end()) {
-        (void)unlink(dst.c_str());
-        if (link(it->second.c_str(), dst.c_str()) == 0) {
-          ++stats.files;
-          return;
-        }
-      }
-      hardlinks[key] = dst;
-    }
-    ++stats.files;
-    stats.bytes += (unsigned long long)st.st_size;
-    if ((size_t)st.st_size <= kSmallCutoff) {
-      small.push_back({src, dst, st});
-      if (small.size() >= 4096) {  // bound memory for the job list
-        copy_small_batch(ring, small, stats);
-        small.clear();
-      }
-      return;
-    }
-    int in_fd = open(src.c_str(), O_RDONLY | O_CLOEXEC);
-    if (in_fd < 0) die("open " + src);
-    int out_fd = open(dst.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0600);
-    if (out_fd < 0) {
-      close(in_fd);
-      die("open " + dst);
-    }
-    copy_data_large(in_fd, out_fd, st.st_size);
-    close(in_fd);
-    close(out_fd);
-    copy_xattrs(src, dst);
-    copy_meta(dst, st);
-  }
-};
-
-CopyStats copy_tree_impl(const std::string& src, const std::string& dst) {
-  Ring ring;
-  (void)ring.init();  // failure => per-file fallback paths
-
-  struct stat st;
-  if (lstat(src.c_str(), &st) != 0) die("lstat " + src);
-  if (!S_ISDIR(st.st_mode)) throw std::runtime_error(src + " is not a directory");
-  if (mkdir(dst.c_str(), st.st_mode & 07777) != 0 && errno != EEXIST)
-    die("mkdir " + dst);
-
-  Walker w(ring);
-  DIR* d = opendir(src.c_str());
-  if (!d) die("opendir " + src);
-  while (dirent* e = readdir(d)) {
-    std::string n(e->d_name);
-    if (n == "." || n == "..") continue;
-    w.walk(src + "/" + n, dst + "/" + n);
-  }
-  closedir(d);
-  copy_small_batch(ring, w.small, w.stats);
-  copy_xattrs(src, dst);
-  for (auto it = w.dir_meta.rbegin(); it != w.dir_meta.rend(); ++it)
-    copy_meta(it->first, it->second);
-  return w.stats;
-}
-
-py::dict copy_tree(const std::string& src, const std::string& dst) {
-  CopyStats stats;
+py::dict copy_tree(const std::string& src, const std::string& dst, bool use_uring,
+                   bool use_copy_file_range) {
+  iocopy::Options opt;
+  opt.use_uring = use_uring;
+  opt.use_copy_file_range = use_copy_file_range;
+  iocopy::CopyStats stats;
   {
     py::gil_scoped_release rel;  // the walk does blocking IO
-    stats = copy_tree_impl(src, dst);
+    stats = iocopy::copy_tree(src, dst, opt);
   }
   py::dict out;
   out["files"] = stats.files;
@@ -511,15 +30,11 @@ py::dict copy_tree(const std::string& src, const std::string& dst) {
   return out;
 }
 
-bool uring_available() {
-  Ring r;
-  return r.init();
-}
-
 }  // namespace
 
 PYBIND11_MODULE(_iocopy, m) {
   m.doc() = "bulk copy engine: io_uring small-file batching + copy_file_range";
-  m.def("copy_tree", &copy_tree, py::arg("src"), py::arg("dst"));
-  m.def("uring_available", &uring_available);
+  m.def("copy_tree", &copy_tree, py::arg("src"), py::arg("dst"), py::kw_only(),
+        py::arg("use_uring") = true, py::arg("use_copy_file_range") = true);
+  m.def("uring_available", &iocopy::uring_available);
 }

@@ -3,7 +3,7 @@
 Artifacts (git-ignored, but shipped by the repo snapshot to GPU boxes):
 
   gpu_docker_api_amd/ops/_hipcore.so   - torch extension (csrc/hipcore.hip)
-  gpu_docker_api_amd/ops/_iocopy.so    - pybind11 module (csrc/iocopy.cpp)
+  gpu_docker_api_amd/ops/_iocopy.so    - pybind11 module (csrc/iocopy.cpp, iocopy_core.h)
   gpu_docker_api_amd/ops/_proclife.so  - pybind11 module (csrc/proclife.cpp)
   csrc/bin/rccl_smoke                  - standalone binary (csrc/rccl_smoke.hip)
 
@@ -83,8 +83,9 @@ def build_hipcore(force: bool = False) -> str:
 
 def build_iocopy(force: bool = False) -> str:
     src = os.path.join(CSRC, "iocopy.cpp")
+    core = os.path.join(CSRC, "iocopy_core.h")
     out = os.path.join(OPS, "_iocopy.so")
-    if not force and _newer(out, src):
+    if not force and _newer(out, src, core):
         return out
     import pybind11
 

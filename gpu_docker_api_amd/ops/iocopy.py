@@ -26,8 +26,17 @@ def _load():
     return mod
 
 
-def copy_tree(src: str, dst: str) -> dict:
-    return _load().copy_tree(src, dst)
+def copy_tree(src, dst, *, use_uring: bool = True, use_copy_file_range: bool = True) -> dict:
+    """Copy the tree under ``src`` into ``dst`` (str or bytes paths).
+
+    The engine picks its data path per file: the io_uring batch for small
+    files, a copy_file_range loop for large or sparse ones, pread/pwrite
+    where the kernel refuses copy_file_range. ``use_uring=False`` sends small
+    files through the per-file path as well, ``use_copy_file_range=False``
+    forces the pread/pwrite bounce."""
+    return _load().copy_tree(
+        src, dst, use_uring=use_uring, use_copy_file_range=use_copy_file_range
+    )
 
 
 def uring_available() -> bool:

@@ -5,12 +5,14 @@ The reference migrates a container's writable layer with a shell tar pipe
 and migrates volumes by spinning up a throwaway ubuntu container that runs
 ``mv`` inside, fire-and-forget (utils/copy.go:74-128). Here:
 
-* the preferred engine is the native io_uring copier (csrc/iocopy.cpp →
+* the preferred engine is the native io_uring copier (csrc/iocopy_core.h →
   ops._iocopy): queued reads/writes, sparse-aware, preserves
-  mode/mtime/symlinks/xattrs (overlayfs whiteouts are device nodes + xattrs,
-  which it replicates);
+  owner/mode/mtime/symlinks/hardlinks/xattrs (overlayfs whiteouts are device
+  nodes + xattrs, which it replicates);
 * the fallback is a shell-free tar pipe (two connected subprocesses with
-  --xattrs) — still awaited, never fire-and-forget;
+  --xattrs --sparse) — still awaited, never fire-and-forget;
+* near-empty layers are copied inline with the same fidelity; what each
+  route must preserve is written down in tests/test_copy_engines.py;
 * volume migration is a plain host-side move (the daemon can see both
   mountpoints; no helper container needed), also awaited.
 """
@@ -20,6 +22,7 @@ import asyncio
 import logging
 import os
 import shutil
+import stat
 import subprocess
 from typing import Optional
 
@@ -52,18 +55,23 @@ def _tar_supports(flag: str) -> bool:
 
 
 _TAR_XATTRS: Optional[bool] = None
+_TAR_SPARSE: Optional[bool] = None
 
 
 async def _tar_pipe_copy(src: str, dest: str) -> None:
-    """tar -C src -c . | tar -C dest -x  (no shell, awaited, xattrs kept)."""
-    global _TAR_XATTRS
+    """tar -C src -c . | tar -C dest -x  (no shell, awaited, xattrs kept,
+    holes kept where tar offers --sparse, modes kept whatever the umask)."""
+    global _TAR_XATTRS, _TAR_SPARSE
     if _TAR_XATTRS is None:
         _TAR_XATTRS = _tar_supports("--xattrs")
+    if _TAR_SPARSE is None:
+        _TAR_SPARSE = _tar_supports("--sparse")
     extra = ["--xattrs", "--acls"] if _TAR_XATTRS else []
+    sparse = ["--sparse"] if _TAR_SPARSE else []
     r_fd, w_fd = os.pipe()
     try:
         reader = await asyncio.create_subprocess_exec(
-            "tar", "-C", src, *extra, "-cf", "-", ".", stdout=w_fd
+            "tar", "-C", src, *extra, *sparse, "-cf", "-", ".", stdout=w_fd
         )
     finally:
         os.close(w_fd)
@@ -73,6 +81,7 @@ async def _tar_pipe_copy(src: str, dest: str) -> None:
             "-C",
             dest,
             *(extra + ["--xattrs-include=*"] if extra else []),
+            "-p",
             "-xf",
             "-",
             stdin=r_fd,
@@ -100,8 +109,10 @@ class CopyEngine:
 
     @classmethod
     def _small_tree_entries(cls, src: str):
-        """Top-level regular files/symlinks totaling <= SMALL_TREE_BYTES,
-        or None when the tree needs a real engine (subdirs/large/special)."""
+        """Top-level regular files/symlinks totaling <= SMALL_TREE_BYTES, as
+        (name, lstat) pairs, or None when the tree needs a real engine:
+        subdirectories, special files, large trees, and what the inline copy
+        does not carry (names of one inode, holes)."""
         entries = []
         total = 0
         try:
@@ -109,18 +120,67 @@ class CopyEngine:
                 for e in it:
                     if len(entries) >= cls.SMALL_TREE_FILES:
                         return None
-                    if e.is_symlink():
-                        entries.append(e)
+                    st = e.stat(follow_symlinks=False)
+                    if stat.S_ISLNK(st.st_mode):
+                        entries.append((e.name, st))
                         continue
-                    if not e.is_file(follow_symlinks=False):
+                    if not stat.S_ISREG(st.st_mode):
                         return None
-                    total += e.stat(follow_symlinks=False).st_size
+                    if st.st_nlink > 1 or st.st_blocks * 512 < st.st_size:
+                        return None
+                    total += st.st_size
                     if total > cls.SMALL_TREE_BYTES:
                         return None
-                    entries.append(e)
+                    entries.append((e.name, st))
         except OSError:
             return None
         return entries
+
+    @staticmethod
+    def _copy_entry_inline(src: str, dest: str, st: os.stat_result) -> None:
+        """One top-level file or symlink with everything the engines keep:
+        content, owner, mode, mtime, xattrs. The destination entry is
+        replaced, never opened or followed."""
+        try:
+            os.unlink(dest)
+        except FileNotFoundError:
+            pass
+        if stat.S_ISLNK(st.st_mode):
+            os.symlink(os.readlink(src), dest)
+        else:
+            in_fd = os.open(src, os.O_RDONLY | os.O_CLOEXEC)
+            try:
+                out_fd = os.open(
+                    dest,
+                    os.O_WRONLY | os.O_CREAT | os.O_EXCL | os.O_NOFOLLOW | os.O_CLOEXEC,
+                    0o600,
+                )
+                try:
+                    left = st.st_size
+                    while left > 0:
+                        chunk = os.read(in_fd, left)
+                        if not chunk:
+                            raise OSError(f"{src}: end of file {left} bytes early")
+                        view = memoryview(chunk)
+                        while view:
+                            view = view[os.write(out_fd, view):]
+                        left -= len(chunk)
+                finally:
+                    os.close(out_fd)
+            finally:
+                os.close(in_fd)
+            for name in os.listxattr(src):
+                try:
+                    os.setxattr(dest, name, os.getxattr(src, name))
+                except OSError:
+                    pass  # best-effort, as in the native engine: security.*
+        try:
+            os.chown(dest, st.st_uid, st.st_gid, follow_symlinks=False)
+        except OSError:
+            pass  # unprivileged
+        if not stat.S_ISLNK(st.st_mode):
+            os.chmod(dest, stat.S_IMODE(st.st_mode))  # after the chown: keeps setuid
+        os.utime(dest, ns=(st.st_atime_ns, st.st_mtime_ns), follow_symlinks=False)
 
     async def copy_dir(self, src: str, dest: str) -> None:
         if not os.path.isdir(src):
@@ -128,15 +188,10 @@ class CopyEngine:
         os.makedirs(dest, exist_ok=True)
         small = self._small_tree_entries(src)
         if small is not None:
-            for e in small:
-                target = os.path.join(dest, e.name)
-                if e.is_symlink():
-                    link = os.readlink(e.path)
-                    if os.path.lexists(target):
-                        os.unlink(target)
-                    os.symlink(link, target)
-                else:
-                    shutil.copy2(e.path, target)
+            for name, st in small:
+                self._copy_entry_inline(
+                    os.path.join(src, name), os.path.join(dest, name), st
+                )
             return
         kind = self.kind
         if kind == "auto":
