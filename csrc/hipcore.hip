@@ -9,6 +9,9 @@
 //     scheduler's adjacency matrix (parallel/topology.py).
 //   * HBM pattern memory test (hbm_memtest.hip): write / verify / verify_flip
 //     over seeded 64-bit words — the burn-in's data-integrity pass.
+//   * Per-CU MFMA and LDS check (cu_check.hip): exact tiles in bf16, MX-fp8
+//     and MX-fp4 checked on the CU that computed them, its whole LDS
+//     pattern-tested, every result tagged with the XCC and CU id.
 //   * MFMA warm-up / validation tiles: the exact-f32 16x16x4 MFMA (operand
 //     maps documented in the CDNA4 guide) and the bf16 16x16x32 MFMA —
 //     clock ramp before measuring, numerics check against torch fp32.
@@ -192,6 +195,7 @@ __global__ void mfma_warmup_kernel(float* __restrict__ sink, int iters) {
 #include "gemm_bf16_8phase.hip"
 #include "gemm_fp8_mx.hip"
 #include "hbm_memtest.hip"
+#include "cu_check.hip"
 
 namespace {
 
@@ -955,6 +959,7 @@ py::dict device_info(int device) {
   d["gcnArchName"] = std::string(prop.gcnArchName);
   d["totalGlobalMem"] = (long long)prop.totalGlobalMem;
   d["multiProcessorCount"] = prop.multiProcessorCount;
+  d["sharedMemPerBlockOptin"] = (long long)prop.sharedMemPerBlockOptin;
   d["pciBusID"] = prop.pciBusID;
   d["pciDomainID"] = prop.pciDomainID;
   d["pciDeviceID"] = prop.pciDeviceID;
@@ -1027,4 +1032,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scrub") = false,
         py::arg("inject") =
             std::vector<std::pair<unsigned long long, unsigned long long>>{});
+  m.def("cu_check", &cu_check::cu_check, py::arg("device"), py::arg("rounds"),
+        py::arg("seed"), py::arg("grid_mult") = 2,
+        py::arg("inject") = std::vector<std::vector<long long>>{});
+  m.def("cu_check_tile", &cu_check::cu_check_tile, py::arg("fmt"),
+        py::arg("tile"), py::arg("seed"));
+  m.def("cu_check_geometry", &cu_check::cu_check_geometry);
 }

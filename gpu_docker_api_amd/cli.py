@@ -251,12 +251,17 @@ def res_validate(
     memtest_mib: int = typer.Option(
         0, "--memtest-mib", help="also pattern-test this many MiB of HBM per GPU (0 = off)"
     ),
+    cu_check: int = typer.Option(
+        0, "--cu-check", help="also check every CU's MFMA and LDS for this many rounds (0 = off)"
+    ),
 ):
     """Burn-in free GPUs (HBM bandwidth + bf16/MX-fp8/MX-fp4 MFMA TFLOPS,
-    optionally an HBM pattern memory test)."""
+    optionally an HBM pattern memory test and a per-CU compute check)."""
     body = {"size": size, "iters": iters}
     if memtest_mib:
         body["memtestMiB"] = memtest_mib
+    if cu_check > 0:
+        body["cuCheck"] = cu_check
     with _client() as c:
         _show(
             c.post(

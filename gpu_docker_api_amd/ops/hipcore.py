@@ -133,12 +133,120 @@ def memtest_gpu(
     return report
 
 
+CU_CHECK_SEED = 0x5EEDC0DEC0FFEE11
+CU_CHECK_ROUNDS = 8
+CU_CHECK_TESTS = ("bf16", "fp8", "fp4", "lds")
+
+
+def hw_id_fields(hw_id: int) -> dict:
+    """HW_REG_HW_ID as the CDNA ISA documents it: wave 3:0, simd 5:4, pipe
+    7:6, cu 11:8, sh 12, se 15:13. The layout is a presentation of the raw
+    word; a CU's identity never rests on it (cu_check_key)."""
+    hw_id = int(hw_id)
+    return {
+        "wave": hw_id & 0xF,
+        "simd": (hw_id >> 4) & 0x3,
+        "pipe": (hw_id >> 6) & 0x3,
+        "cu": (hw_id >> 8) & 0xF,
+        "sh": (hw_id >> 12) & 0x1,
+        "se": (hw_id >> 13) & 0x7,
+    }
+
+
+def cu_check_key(record: dict) -> int:
+    """The CU a workgroup ran on: xcc << 8 | HW_ID bits 15:8 (SE, SH and CU
+    together) of its first wave, raw."""
+    return (int(record["xcc"]) & 0xF) << 8 | (int(record["hw_id"][0]) >> 8) & 0xFF
+
+
+def cu_check_fold(records: list, cus_expected: int) -> dict:
+    """Fold the per-workgroup records of cu_check by the CU they ran on.
+    Pure Python. `bad_cus` lists every CU with a mismatch, with its counts per
+    test and the first mismatch one of its workgroups reported. Coverage
+    (`cus_seen` against `cus_expected`) is reported, never judged: a busy GPU
+    places workgroups unevenly."""
+    cus: dict = {}
+    simds = set()
+    split = 0
+    errors = {t: 0 for t in CU_CHECK_TESTS}
+    for rec in records:
+        key = cu_check_key(rec)
+        if len({(int(h) >> 8) & 0xFF for h in rec["hw_id"]}) > 1:
+            split += 1  # waves of one workgroup on different "CUs": layout is off
+        simds.update(hw_id_fields(h)["simd"] for h in rec["hw_id"])
+        cu = cus.setdefault(
+            key, {"workgroups": 0, "tests": {t: 0 for t in CU_CHECK_TESTS}, "first": None}
+        )
+        cu["workgroups"] += 1
+        for t in CU_CHECK_TESTS:
+            n = int(rec["counts"].get(t, 0))
+            cu["tests"][t] += n
+            errors[t] += n
+        if cu["first"] is None and rec.get("first") is not None:
+            cu["first"] = dict(rec["first"])
+            wave = int(cu["first"].get("wave", 0))
+            if 0 <= wave < len(rec["hw_id"]):  # the SIMD that wave ran on
+                cu["first"]["simd"] = hw_id_fields(rec["hw_id"][wave])["simd"]
+    per_xcc: dict = {}
+    for key in cus:
+        per_xcc[key >> 8] = per_xcc.get(key >> 8, 0) + 1
+    bad = []
+    for key in sorted(cus):
+        cu = cus[key]
+        if sum(cu["tests"].values()) == 0:
+            continue
+        f = hw_id_fields(key << 8)
+        bad.append(
+            {
+                "xcc": key >> 8,
+                "se": f["se"],
+                "sh": f["sh"],
+                "cu": f["cu"],
+                "key": key,
+                "tests": dict(cu["tests"]),
+                "first": cu["first"],
+            }
+        )
+    return {
+        "cus_expected": int(cus_expected),
+        "cus_seen": len(cus),
+        "xccs": [{"xcc": x, "cus": per_xcc[x]} for x in sorted(per_xcc)],
+        "simds_seen": sorted(simds),
+        "workgroups": len(records),
+        "split_workgroups": split,
+        "errors": {"total": sum(errors.values()), **errors},
+        "bad_cus": bad,
+    }
+
+
+def cu_check_gpu(
+    index: int,
+    rounds: int = CU_CHECK_ROUNDS,
+    seed: int = CU_CHECK_SEED,
+    inject: Optional[list] = None,
+) -> dict:
+    """Per-CU compute check of GPU `index` (csrc/cu_check.hip): every CU
+    computes `rounds` x 4 exact tiles in bf16, MX-fp8 and MX-fp4, compares
+    them with integer arithmetic on the spot and pattern-tests its whole LDS.
+    Returns the fold by CU plus how the pass ran."""
+    ext = load_ext()
+    cus = int(ext.device_info(index)["multiProcessorCount"])
+    raw = ext.cu_check(index, int(rounds), seed, 2, list(inject or []))
+    report = cu_check_fold(raw["records"], cus)
+    report["rounds"] = int(rounds)
+    report["launches"] = raw["launches"]
+    report["lds_bytes"] = raw["lds_bytes"]
+    report["seconds"] = round(raw["seconds"], 4)
+    return report
+
+
 def validate_gpus(
     indices: Optional[list] = None,
     size: int = 4096,
     iters: int = 5,
     fp8: bool = True,
     memtest_mib: int = 0,
+    cu_rounds: int = 0,
 ) -> dict:
     """Per-GPU health burn-in: HBM stream bandwidth + dense bf16 MFMA GEMM
     (the 8-phase 256^2 structure, ~1.1 PF) + the MX-fp8 path (block-scaled
@@ -146,7 +254,10 @@ def validate_gpus(
     tenants run on MI355X and its datapath can fail independently of bf16).
     Run on FREE GPUs before scheduling; a GPU far below its siblings is
     flagged. With memtest_mib > 0 each GPU also gets the HBM pattern test
-    (memtest_gpu) and is unhealthy if a single word read back wrong."""
+    (memtest_gpu) and is unhealthy if a single word read back wrong. With
+    cu_rounds > 0 each GPU also gets the per-CU MFMA and LDS check
+    (cu_check_gpu) and is unhealthy if a single result or LDS word was wrong;
+    CUs the pass did not reach are reported, not judged."""
     ext = load_ext()
     n = ext.device_count()
     idx = list(indices) if indices else list(range(n))
@@ -173,6 +284,8 @@ def validate_gpus(
             entry["fp4_tflops"] = round(ext.gemm_fp4_mx_tflops(i, size, iters), 1)
         if memtest_mib > 0:
             entry["memtest"] = memtest_gpu(i, memtest_mib)
+        if cu_rounds > 0:
+            entry["cu_check"] = cu_check_gpu(i, cu_rounds)
         report["gpus"].append(entry)
     vals = [g["bf16_tflops"] for g in report["gpus"]]
     if vals:
@@ -181,14 +294,23 @@ def validate_gpus(
             g["healthy"] = bool(g["bf16_tflops"] > 0.7 * top and g["hbm_gbps"] > 2000)
             if "memtest" in g and "errors" in g["memtest"]:
                 g["healthy"] = bool(g["healthy"] and g["memtest"]["errors"] == 0)
+            if "cu_check" in g:
+                g["healthy"] = bool(g["healthy"] and g["cu_check"]["errors"]["total"] == 0)
     return report
 
 
 async def validate_gpus_async(
-    indices: Optional[list] = None, size: int = 4096, iters: int = 5, memtest_mib: int = 0
+    indices: Optional[list] = None,
+    size: int = 4096,
+    iters: int = 5,
+    memtest_mib: int = 0,
+    cu_rounds: int = 0,
 ) -> dict:
     return await asyncio.get_running_loop().run_in_executor(
-        None, lambda: validate_gpus(indices, size, iters, memtest_mib=memtest_mib)
+        None,
+        lambda: validate_gpus(
+            indices, size, iters, memtest_mib=memtest_mib, cu_rounds=cu_rounds
+        ),
     )
 
 

@@ -25,9 +25,9 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
     @r.post("/gpus/validate")
     async def gpus_validate(request: Request):
         """MI355X extension: burn-in the node's FREE GPUs (HBM bandwidth +
-        dense bf16 MFMA GEMM, and with `memtestMiB` an HBM pattern memory
-        test) before trusting them with placements. Busy GPUs are skipped
-        unless explicitly listed."""
+        dense bf16 MFMA GEMM, with `memtestMiB` an HBM pattern memory test
+        and with `cuCheck` a per-CU MFMA and LDS check) before trusting them
+        with placements. Busy GPUs are skipped unless explicitly listed."""
         try:
             body = await request.json()
         except Exception:
@@ -55,6 +55,9 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
             memtest = body.get("memtestMiB", 0)
             if isinstance(memtest, bool) or not isinstance(memtest, int):
                 raise TypeError("memtestMiB must be an int")
+            cu_rounds = body.get("cuCheck", 0)
+            if isinstance(cu_rounds, bool) or not isinstance(cu_rounds, int):
+                raise TypeError("cuCheck must be an int")
         except (TypeError, ValueError):
             from .codes import Code
             from .response import error
@@ -66,11 +69,16 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
             # HBM pattern test: off at 0, else 1 GiB .. the whole 288 GB card
             if memtest != 0:
                 memtest = max(1024, min(memtest, 294912))
+            # per-CU compute check: off at 0, else 1 .. 4096 rounds
+            extra = {}
+            if cu_rounds != 0:
+                extra["cu_rounds"] = max(1, min(cu_rounds, 4096))
             report = await hipcore.validate_gpus_async(
                 idx,
                 max(256, min(size, 16384)),
                 max(1, min(iters, 50)),
                 memtest_mib=memtest,
+                **extra,
             )
         except Exception as exc:  # noqa: BLE001 — no GPU / extension absent
             from .codes import Code
