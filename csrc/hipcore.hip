@@ -22,12 +22,12 @@
 // Build: hipcc --offload-arch=gfx950 (driven by gpu_docker_api_amd/ops/build.py).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include <map>
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
 #include <algorithm>
 #include <functional>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -218,9 +218,17 @@ __global__ void fill_bf16_hash_kernel(__hip_bfloat16* p, size_t n, unsigned seed
 // Host-side probe machinery
 // ---------------------------------------------------------------------------
 
+// Owns `count` elements of device memory on `device`.
+template <typename T>
 struct DeviceBuf {
-  float* ptr = nullptr;
-  int device = -1;
+  T* ptr = nullptr;
+  int device;
+  DeviceBuf(int device, size_t count) : device(device) {
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipMalloc(&ptr, count * sizeof(T)));
+  }
+  DeviceBuf(const DeviceBuf&) = delete;
+  DeviceBuf& operator=(const DeviceBuf&) = delete;
   ~DeviceBuf() {
     if (ptr) {
       (void)hipSetDevice(device);
@@ -264,10 +272,7 @@ double stream_bandwidth_gbps(int device, int mib, int iters) {
   size_t n = (size_t)mib * 1024 * 1024 / sizeof(float);
   HIP_CHECK(hipSetDevice(device));
   mfma_warmup(device, 2000);
-  DeviceBuf src, dst;
-  src.device = dst.device = device;
-  HIP_CHECK(hipMalloc(&src.ptr, n * sizeof(float)));
-  HIP_CHECK(hipMalloc(&dst.ptr, n * sizeof(float)));
+  DeviceBuf<float> src(device, n), dst(device, n);
   HIP_CHECK(hipMemset(src.ptr, 1, n * sizeof(float)));
   double ms = time_kernel_ms(
       device,
@@ -279,10 +284,7 @@ double stream_bandwidth_gbps(int device, int mib, int iters) {
 double memcpy_bandwidth_gbps(int device, int mib, int iters) {
   size_t n = (size_t)mib * 1024 * 1024 / sizeof(float);
   HIP_CHECK(hipSetDevice(device));
-  DeviceBuf src, dst;
-  src.device = dst.device = device;
-  HIP_CHECK(hipMalloc(&src.ptr, n * sizeof(float)));
-  HIP_CHECK(hipMalloc(&dst.ptr, n * sizeof(float)));
+  DeviceBuf<float> src(device, n), dst(device, n);
   HIP_CHECK(hipMemset(src.ptr, 1, n * sizeof(float)));
   double ms = time_kernel_ms(
       device,
@@ -305,14 +307,9 @@ double p2p_bandwidth_gbps(int src_dev, int dst_dev, int mib, int iters) {
   int can_access = 0;
   HIP_CHECK(hipDeviceCanAccessPeer(&can_access, dst_dev, src_dev));
 
-  DeviceBuf src, dst;
-  src.device = src_dev;
-  dst.device = dst_dev;
-  HIP_CHECK(hipSetDevice(src_dev));
-  HIP_CHECK(hipMalloc(&src.ptr, n * sizeof(float)));
+  DeviceBuf<float> src(src_dev, n);
   HIP_CHECK(hipMemset(src.ptr, 1, n * sizeof(float)));
-  HIP_CHECK(hipSetDevice(dst_dev));
-  HIP_CHECK(hipMalloc(&dst.ptr, n * sizeof(float)));
+  DeviceBuf<float> dst(dst_dev, n);
 
   if (can_access) {
     hipError_t e = hipDeviceEnablePeerAccess(src_dev, 0);
@@ -565,99 +562,147 @@ torch::Tensor gemm_bf16_bt(torch::Tensor A, torch::Tensor Bt, int swizzle,
   return C;
 }
 
+// Enqueues one size^3 GEMM on a stream: (stream, A, Bt, C).
+template <typename T>
+using GemmLaunch = std::function<void(hipStream_t, const T*, const T*, float*)>;
+
+// One size^3 throughput measurement, shared by every *_tflops / _ab driver:
+// MFMA warm-up, three owned device buffers (released on any exit), hash-filled
+// operands, then each of `launches` timed once per round, round-robin.
+// operand_elems: stored elements per operand (size^2; halved for packed fp4).
+// Returns TF (2*size^3 flop) as [round][launch].
+template <typename T>
+std::vector<std::vector<double>> time_gemm_tflops(
+    int device, int size, int iters, int rounds, size_t operand_elems,
+    void (*fill)(T*, size_t, unsigned), const std::vector<GemmLaunch<T>>& launches) {
+  HIP_CHECK(hipSetDevice(device));
+  mfma_warmup(device, 20000);
+  DeviceBuf<T> A(device, operand_elems), Bt(device, operand_elems);
+  DeviceBuf<float> C(device, (size_t)size * size);
+  hipLaunchKernelGGL(fill, dim3(4096), dim3(256), 0, 0, A.ptr, operand_elems, 1u);
+  hipLaunchKernelGGL(fill, dim3(4096), dim3(256), 0, 0, Bt.ptr, operand_elems, 7u);
+  HIP_CHECK(hipDeviceSynchronize());
+  std::vector<std::vector<double>> tf(rounds);
+  for (auto& round : tf) {
+    for (const auto& launch : launches) {
+      double ms = time_kernel_ms(
+          device, [&](hipStream_t s) { launch(s, A.ptr, Bt.ptr, C.ptr); }, iters);
+      round.push_back(2.0 * size * (double)size * size / (ms * 1e9));
+    }
+  }
+  return tf;
+}
+
 // Dense bf16 throughput on one device (the health-check burn-in number).
 double gemm_bf16_tflops(int device, int size, int iters, int swizzle, int bk) {
   if (bk != 32) bk = 64;  // historical: anything but 32 times the BK=64 kernel
   TORCH_CHECK(size >= 128 && size % 128 == 0, "size must be a multiple of 128");
   bk = resolve_bf16_bk(bk, size);
-  HIP_CHECK(hipSetDevice(device));
-  mfma_warmup(device, 20000);
-  size_t n = (size_t)size * size;
-  __hip_bfloat16 *A = nullptr, *Bt = nullptr;
-  float* C = nullptr;
-  HIP_CHECK(hipMalloc(&A, n * sizeof(__hip_bfloat16)));
-  HIP_CHECK(hipMalloc(&Bt, n * sizeof(__hip_bfloat16)));
-  HIP_CHECK(hipMalloc(&C, n * sizeof(float)));
-  hipLaunchKernelGGL(fill_bf16_hash_kernel, dim3(4096), dim3(256), 0, 0, A, n, 1u);
-  hipLaunchKernelGGL(fill_bf16_hash_kernel, dim3(4096), dim3(256), 0, 0, Bt, n, 7u);
-  HIP_CHECK(hipDeviceSynchronize());
   int grid = (size / 128) * (size / 128);
-  double ms = time_kernel_ms(
-      device,
-      [&](hipStream_t s) {
+  return time_gemm_tflops<__hip_bfloat16>(
+      device, size, iters, 1, (size_t)size * size, fill_bf16_hash_kernel,
+      {[=](hipStream_t s, const __hip_bfloat16* A, const __hip_bfloat16* Bt,
+           float* C) {
         launch_bf16_tile(bk, swizzle, dim3(grid), s, A, Bt, C, size, size, size);
-      },
-      iters);
-  (void)hipFree(A);
-  (void)hipFree(Bt);
-  (void)hipFree(C);
-  return 2.0 * size * (double)size * size / (ms * 1e9);
+      }})[0][0];
 }
 
-// variant encoding: bit0 = XCD remap (T1), bits>=1 = schedule:
-// 0/1 = <XCD,PIPE=0> round-1 schedule; 2/3 = <XCD,PIPE=1> phase-ahead;
-// 4/5 = <XCD,PIPE=2> 2-tile-unrolled; 6/7 = <XCD,PIPE=3> unrolled,
-// compiler-managed lgkm waits; 8/9 = <XCD,PIPE=4> merged phases 2+3;
-// 10/11 = <XCD,PIPE=5> static-setprio younger half.
-void launch_8ph(int variant, dim3 grid, hipStream_t s,
-                const __hip_bfloat16* A, const __hip_bfloat16* Bt, float* C,
-                int M, int N, int K) {
-  switch (variant) {
-    case 1:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, 0>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 2:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, 1>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 3:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, 1>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 4:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, 2>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 5:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, 2>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 6:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, 3>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 7:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, 3>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 8:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, 4>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 9:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, 4>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 10:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, 5>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 11:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, 5>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 12:  // PIPE=0 schedule + row-bit-3 LDS swizzle
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, 0, 1>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 0:
-      hipLaunchKernelGGL((gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, 0>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    default:
-      TORCH_CHECK(false, "unknown 8-phase variant ", variant, " (0..12)");
-  }
+// ---------------------------------------------------------------------------
+// 256^2 8-phase family: one {code, kernel} table per operand format, shared by
+// the tensor bindings and the timing drivers so the numerics tests cover
+// exactly the kernels that are timed. Tables are in ascending code order; the
+// "known codes" text of the errors is generated from them.
+// ---------------------------------------------------------------------------
+
+template <typename T>
+using Gemm256Kernel = void (*)(const T*, const T*, float*, int, int, int);
+
+template <typename T>
+struct Gemm256Variant {
+  int code;
+  Gemm256Kernel<T> kernel;
+};
+
+// bit0 = XCD remap; schedules are described in gemm_bf16_8phase.hip.
+// Template axes: <XCD, SCHED, SWZV>.
+constexpr Gemm256Variant<__hip_bfloat16> kBf16Variants8ph[] = {
+    {0, gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, gemm_bf16_8ph::ROLLED>},
+    {1, gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, gemm_bf16_8ph::ROLLED>},
+    {2, gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, gemm_bf16_8ph::PHASE_AHEAD>},
+    {3, gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, gemm_bf16_8ph::PHASE_AHEAD>},
+    {4, gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, gemm_bf16_8ph::UNROLLED_FENCED>},
+    {5, gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, gemm_bf16_8ph::UNROLLED_FENCED>},
+    {6, gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, gemm_bf16_8ph::UNROLLED>},
+    {7, gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, gemm_bf16_8ph::UNROLLED>},
+    // 10, 11: aliases of 6, 7, the kernels these codes always ran (8 and 9,
+    // the other two such codes, are rejected; gemm_bf16_8phase.hip)
+    {10, gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, gemm_bf16_8ph::UNROLLED>},
+    {11, gemm_bf16_8ph::gemm_bf16_8phase_kernel<1, gemm_bf16_8ph::UNROLLED>},
+    {12, gemm_bf16_8ph::gemm_bf16_8phase_kernel<0, gemm_bf16_8ph::ROLLED, 1>},
+};
+
+// Template axes: <FMT, SWZV, EPI, MP23>.
+constexpr Gemm256Variant<unsigned char> kFp8MxShapes[] = {
+    // default: row-bit-3 swizzle (conflict-free 2-chunk reads, +11%)
+    {16, gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 0, 0>},
+    // legacy row&7-only swizzle (A/B reference)
+    {17, gemm_fp8_mx::gemm_fp8_mx_kernel<0, 0, 0, 0>},
+    // + quad-transpose dwordx4 epilogue
+    {18, gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 1, 0>},
+    // merged phases 2+3
+    {20, gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 0, 1>},
+    // 32x32x64 instruction
+    {32, gemm_fp8_mx::gemm_mx32_kernel<0, 0>},
+};
+
+// Code 16 (the default) and 19 are the same instantiation.
+constexpr Gemm256Variant<unsigned char> kFp4MxShapes[] = {
+    // default: merged phases 2+3 (+1-2% measured both orders)
+    {16, gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 1>},
+    // 16x16 with the row-bit-3 swizzle
+    {17, gemm_fp8_mx::gemm_fp8_mx_kernel<4, 1, 0, 0>},
+    // + quad-transpose dwordx4 epilogue
+    {18, gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 1, 0>},
+    {19, gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 1>},
+    // unmerged legacy (A/B reference)
+    {21, gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 0>},
+    // 32x32x64 instruction
+    {32, gemm_fp8_mx::gemm_mx32_kernel<4, 0>},
+};
+
+// The kernel for `code`, or an error naming `what`, the code and the known ones.
+template <typename T, size_t N>
+Gemm256Kernel<T> find_variant(const Gemm256Variant<T> (&table)[N], int code,
+                              const char* what) {
+  for (const auto& v : table)
+    if (v.code == code) return v.kernel;
+  std::string known;
+  for (const auto& v : table)
+    known += (known.empty() ? "" : ", ") + std::to_string(v.code);
+  TORCH_CHECK(false, "unknown ", what, " ", code, " (", known, ")");
+  return nullptr;  // not reached
+}
+
+template <typename T>
+void launch_256(Gemm256Kernel<T> kernel, hipStream_t s, const T* A, const T* Bt,
+                float* C, int M, int N, int K) {
+  hipLaunchKernelGGL(kernel, dim3((M / 256) * (N / 256)), dim3(512), 0, s, A, Bt,
+                     C, M, N, K);
+}
+
+// size^3 throughput of each of `kernels`, [round][kernel].
+template <typename T>
+std::vector<std::vector<double>> time_256_tflops(
+    int device, int size, int iters, int rounds, size_t operand_elems,
+    void (*fill)(T*, size_t, unsigned),
+    const std::vector<Gemm256Kernel<T>>& kernels) {
+  std::vector<GemmLaunch<T>> launches;
+  for (auto kernel : kernels)
+    launches.push_back([=](hipStream_t s, const T* A, const T* Bt, float* C) {
+      launch_256(kernel, s, A, Bt, C, size, size, size);
+    });
+  return time_gemm_tflops<T>(device, size, iters, rounds, operand_elems, fill,
+                             launches);
 }
 
 torch::Tensor gemm_bf16_8ph_bt(torch::Tensor A, torch::Tensor Bt, int variant,
@@ -672,15 +717,13 @@ torch::Tensor gemm_bf16_8ph_bt(torch::Tensor A, torch::Tensor Bt, int variant,
   TORCH_CHECK(M >= 256 && N >= 256 && M % 256 == 0 && N % 256 == 0 &&
                   K % 64 == 0 && K >= 192,
               "M,N multiples of 256; K multiple of 64, >= 192");
-  TORCH_CHECK(variant >= 0 && variant <= 12, "unknown 8-phase variant ",
-              variant, " (0..12)");
+  auto kernel = find_variant(kBf16Variants8ph, variant, "8-phase variant");
   check_aligned16(A, "A");
   check_aligned16(Bt, "Bt");
   auto C = resolve_out(out, M, N, A);
   check_aligned16(C, "out");
-  int grid = (M / 256) * (N / 256);
   auto stream = at::hip::getCurrentHIPStream();
-  launch_8ph(variant, dim3(grid), stream.stream(),
+  launch_256(kernel, stream.stream(),
              reinterpret_cast<const __hip_bfloat16*>(A.data_ptr()),
              reinterpret_cast<const __hip_bfloat16*>(Bt.data_ptr()),
              C.data_ptr<float>(), M, N, K);
@@ -688,31 +731,11 @@ torch::Tensor gemm_bf16_8ph_bt(torch::Tensor A, torch::Tensor Bt, int variant,
 }
 
 double gemm_bf16_8ph_tflops(int device, int size, int iters, int variant) {
-  TORCH_CHECK(variant >= 0 && variant <= 12, "unknown 8-phase variant ",
-              variant, " (0..12)");
+  auto kernel = find_variant(kBf16Variants8ph, variant, "8-phase variant");
   TORCH_CHECK(size >= 256 && size % 256 == 0, "size must be a multiple of 256");
-  HIP_CHECK(hipSetDevice(device));
-  mfma_warmup(device, 20000);
-  size_t n = (size_t)size * size;
-  __hip_bfloat16 *A = nullptr, *Bt = nullptr;
-  float* C = nullptr;
-  HIP_CHECK(hipMalloc(&A, n * sizeof(__hip_bfloat16)));
-  HIP_CHECK(hipMalloc(&Bt, n * sizeof(__hip_bfloat16)));
-  HIP_CHECK(hipMalloc(&C, n * sizeof(float)));
-  hipLaunchKernelGGL(fill_bf16_hash_kernel, dim3(4096), dim3(256), 0, 0, A, n, 1u);
-  hipLaunchKernelGGL(fill_bf16_hash_kernel, dim3(4096), dim3(256), 0, 0, Bt, n, 7u);
-  HIP_CHECK(hipDeviceSynchronize());
-  int grid = (size / 256) * (size / 256);
-  double ms = time_kernel_ms(
-      device,
-      [&](hipStream_t s) {
-        launch_8ph(variant, dim3(grid), s, A, Bt, C, size, size, size);
-      },
-      iters);
-  (void)hipFree(A);
-  (void)hipFree(Bt);
-  (void)hipFree(C);
-  return 2.0 * size * (double)size * size / (ms * 1e9);
+  return time_256_tflops<__hip_bfloat16>(device, size, iters, 1,
+                                         (size_t)size * size,
+                                         fill_bf16_hash_kernel, {kernel})[0][0];
 }
 
 // Within-probe interleaved A/B over the template variants (guide §5.4
@@ -720,111 +743,20 @@ double gemm_bf16_8ph_tflops(int device, int size, int iters, int variant) {
 // process). Returns {variant: [tflops per round]}.
 py::dict gemm_bf16_8ph_ab(int device, int size, int iters, int rounds,
                           std::vector<int> variants) {
+  std::vector<Gemm256Kernel<__hip_bfloat16>> kernels;
   for (int v : variants)
-    TORCH_CHECK(v >= 0 && v <= 12, "unknown 8-phase variant ", v, " (0..12)");
+    kernels.push_back(find_variant(kBf16Variants8ph, v, "8-phase variant"));
   TORCH_CHECK(size >= 256 && size % 256 == 0, "size must be a multiple of 256");
-  HIP_CHECK(hipSetDevice(device));
-  mfma_warmup(device, 20000);
-  size_t n = (size_t)size * size;
-  __hip_bfloat16 *A = nullptr, *Bt = nullptr;
-  float* C = nullptr;
-  HIP_CHECK(hipMalloc(&A, n * sizeof(__hip_bfloat16)));
-  HIP_CHECK(hipMalloc(&Bt, n * sizeof(__hip_bfloat16)));
-  HIP_CHECK(hipMalloc(&C, n * sizeof(float)));
-  hipLaunchKernelGGL(fill_bf16_hash_kernel, dim3(4096), dim3(256), 0, 0, A, n, 1u);
-  hipLaunchKernelGGL(fill_bf16_hash_kernel, dim3(4096), dim3(256), 0, 0, Bt, n, 7u);
-  HIP_CHECK(hipDeviceSynchronize());
-  int grid = (size / 256) * (size / 256);
+  auto tf = time_256_tflops<__hip_bfloat16>(device, size, iters, rounds,
+                                            (size_t)size * size,
+                                            fill_bf16_hash_kernel, kernels);
   std::map<int, std::vector<double>> out;
-  for (int r = 0; r < rounds; ++r) {
-    for (int v : variants) {
-      double ms = time_kernel_ms(
-          device,
-          [&](hipStream_t s) {
-            launch_8ph(v, dim3(grid), s, A, Bt, C, size, size, size);
-          },
-          iters);
-      out[v].push_back(2.0 * size * (double)size * size / (ms * 1e9));
-    }
-  }
-  (void)hipFree(A);
-  (void)hipFree(Bt);
-  (void)hipFree(C);
+  for (const auto& round : tf)
+    for (size_t i = 0; i < variants.size(); ++i)
+      out[variants[i]].push_back(round[i]);
   py::dict d;
   for (auto& kv : out) d[py::int_(kv.first)] = kv.second;
   return d;
-}
-
-// The one shape -> instantiation table of the MX fp8 GEMM, shared by the
-// tensor binding and gemm_fp8_mx_tflops so the numerics tests cover exactly
-// the kernels that are timed. Template axes: <FMT, SWZV, EPI, MP23>.
-bool fp8_mx_shape_known(int shape) {
-  return shape == 16 || shape == 17 || shape == 18 || shape == 20 || shape == 32;
-}
-
-void launch_fp8_mx(int shape, dim3 grid, hipStream_t s, const unsigned char* A,
-                   const unsigned char* Bt, float* C, int M, int N, int K) {
-  switch (shape) {
-    case 32:  // 32x32x64 instruction
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_mx32_kernel<0, 0>), grid, dim3(512),
-                         0, s, A, Bt, C, M, N, K);
-      break;
-    case 20:  // merged phases 2+3
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 0, 1>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 18:  // + quad-transpose dwordx4 epilogue
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 1, 0>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 17:  // legacy row&7-only swizzle (A/B reference)
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 0, 0, 0>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 16:  // default: row-bit-3 swizzle (conflict-free 2-chunk reads, +11%)
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<0, 1, 0, 0>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    default:
-      TORCH_CHECK(false, "unknown fp8 MX shape code ", shape,
-                  " (16, 17, 18, 20, 32)");
-  }
-}
-
-// Same for MX fp4. Code 16 (the default) and 19 are the same instantiation.
-bool fp4_mx_shape_known(int shape) {
-  return shape == 16 || shape == 17 || shape == 18 || shape == 19 ||
-         shape == 21 || shape == 32;
-}
-
-void launch_fp4_mx(int shape, dim3 grid, hipStream_t s, const unsigned char* A,
-                   const unsigned char* Bt, float* C, int M, int N, int K) {
-  switch (shape) {
-    case 32:  // 32x32x64 instruction
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_mx32_kernel<4, 0>), grid, dim3(512),
-                         0, s, A, Bt, C, M, N, K);
-      break;
-    case 18:  // + quad-transpose dwordx4 epilogue
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 1, 0>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 17:  // 16x16 with the row-bit-3 swizzle
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 1, 0, 0>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 21:  // unmerged legacy (A/B reference)
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 0>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    case 16:  // default: merged phases 2+3 (+1-2% measured both orders)
-    case 19:
-      hipLaunchKernelGGL((gemm_fp8_mx::gemm_fp8_mx_kernel<4, 0, 0, 1>), grid,
-                         dim3(512), 0, s, A, Bt, C, M, N, K);
-      break;
-    default:
-      TORCH_CHECK(false, "unknown fp4 MX shape code ", shape,
-                  " (16, 17, 18, 19, 21, 32)");
-  }
 }
 
 torch::Tensor gemm_fp8_mx_bt(torch::Tensor A, torch::Tensor Bt, int shape,
@@ -840,18 +772,16 @@ torch::Tensor gemm_fp8_mx_bt(torch::Tensor A, torch::Tensor Bt, int shape,
   TORCH_CHECK(M >= 256 && N >= 256 && M % 256 == 0 && N % 256 == 0 &&
                   K % 128 == 0 && K >= 256,
               "M,N multiples of 256; K multiple of 128, >= 256");
-  TORCH_CHECK(fp8_mx_shape_known(shape), "unknown fp8 MX shape code ", shape,
-              " (16, 17, 18, 20, 32)");
+  auto kernel = find_variant(kFp8MxShapes, shape, "fp8 MX shape code");
   check_aligned16(A, "A");
   check_aligned16(Bt, "Bt");
   auto C = resolve_out(out, M, N, A);
   check_aligned16(C, "out");
-  int grid = (M / 256) * (N / 256);
   auto stream = at::hip::getCurrentHIPStream();
-  launch_fp8_mx(shape, dim3(grid), stream.stream(),
-                reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                C.data_ptr<float>(), M, N, K);
+  launch_256(kernel, stream.stream(),
+             reinterpret_cast<const unsigned char*>(A.data_ptr()),
+             reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
+             C.data_ptr<float>(), M, N, K);
   return C;
 }
 
@@ -869,80 +799,36 @@ torch::Tensor gemm_fp4_mx_bt(torch::Tensor A, torch::Tensor Bt, int K, int shape
   TORCH_CHECK(M >= 256 && N >= 256 && M % 256 == 0 && N % 256 == 0 &&
                   K % 256 == 0 && K >= 512,
               "M,N multiples of 256; K multiple of 256, >= 512");
-  TORCH_CHECK(fp4_mx_shape_known(shape), "unknown fp4 MX shape code ", shape,
-              " (16, 17, 18, 19, 21, 32)");
+  auto kernel = find_variant(kFp4MxShapes, shape, "fp4 MX shape code");
   check_aligned16(A, "A");
   check_aligned16(Bt, "Bt");
   auto C = resolve_out(out, M, N, A);
   check_aligned16(C, "out");
-  int grid = (M / 256) * (N / 256);
   auto stream = at::hip::getCurrentHIPStream();
-  launch_fp4_mx(shape, dim3(grid), stream.stream(),
-                reinterpret_cast<const unsigned char*>(A.data_ptr()),
-                reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-                C.data_ptr<float>(), M, N, K);
+  launch_256(kernel, stream.stream(),
+             reinterpret_cast<const unsigned char*>(A.data_ptr()),
+             reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
+             C.data_ptr<float>(), M, N, K);
   return C;
 }
 
 double gemm_fp8_mx_tflops(int device, int size, int iters, int shape) {
-  TORCH_CHECK(fp8_mx_shape_known(shape), "unknown fp8 MX shape code ", shape,
-              " (16, 17, 18, 20, 32)");
+  auto kernel = find_variant(kFp8MxShapes, shape, "fp8 MX shape code");
   TORCH_CHECK(size >= 256 && size % 256 == 0, "size must be a multiple of 256");
-  HIP_CHECK(hipSetDevice(device));
-  mfma_warmup(device, 20000);
-  size_t n = (size_t)size * size;
-  unsigned char *A = nullptr, *Bt = nullptr;
-  float* C = nullptr;
-  HIP_CHECK(hipMalloc(&A, n));
-  HIP_CHECK(hipMalloc(&Bt, n));
-  HIP_CHECK(hipMalloc(&C, n * sizeof(float)));
-  hipLaunchKernelGGL(gemm_fp8_mx::fill_e4m3_hash_kernel, dim3(4096), dim3(256),
-                     0, 0, A, n, 1u);
-  hipLaunchKernelGGL(gemm_fp8_mx::fill_e4m3_hash_kernel, dim3(4096), dim3(256),
-                     0, 0, Bt, n, 7u);
-  HIP_CHECK(hipDeviceSynchronize());
-  int grid = (size / 256) * (size / 256);
-  double ms = time_kernel_ms(
-      device,
-      [&](hipStream_t s) {
-        launch_fp8_mx(shape, dim3(grid), s, A, Bt, C, size, size, size);
-      },
-      iters);
-  (void)hipFree(A);
-  (void)hipFree(Bt);
-  (void)hipFree(C);
-  return 2.0 * size * (double)size * size / (ms * 1e9);
+  return time_256_tflops<unsigned char>(device, size, iters, 1,
+                                        (size_t)size * size,
+                                        gemm_fp8_mx::fill_e4m3_hash_kernel,
+                                        {kernel})[0][0];
 }
 
 double gemm_fp4_mx_tflops(int device, int size, int iters, int shape) {
-  TORCH_CHECK(fp4_mx_shape_known(shape), "unknown fp4 MX shape code ", shape,
-              " (16, 17, 18, 19, 21, 32)");
+  auto kernel = find_variant(kFp4MxShapes, shape, "fp4 MX shape code");
   TORCH_CHECK(size >= 512 && size % 256 == 0,
               "size must be a multiple of 256, >= 512");
-  HIP_CHECK(hipSetDevice(device));
-  mfma_warmup(device, 20000);
-  size_t nb = (size_t)size * size / 2;  // nibble-packed
-  unsigned char *A = nullptr, *Bt = nullptr;
-  float* C = nullptr;
-  HIP_CHECK(hipMalloc(&A, nb));
-  HIP_CHECK(hipMalloc(&Bt, nb));
-  HIP_CHECK(hipMalloc(&C, (size_t)size * size * sizeof(float)));
-  hipLaunchKernelGGL(gemm_fp8_mx::fill_e2m1_hash_kernel, dim3(4096), dim3(256),
-                     0, 0, A, nb, 1u);
-  hipLaunchKernelGGL(gemm_fp8_mx::fill_e2m1_hash_kernel, dim3(4096), dim3(256),
-                     0, 0, Bt, nb, 7u);
-  HIP_CHECK(hipDeviceSynchronize());
-  int grid = (size / 256) * (size / 256);
-  double ms = time_kernel_ms(
-      device,
-      [&](hipStream_t s) {
-        launch_fp4_mx(shape, dim3(grid), s, A, Bt, C, size, size, size);
-      },
-      iters);
-  (void)hipFree(A);
-  (void)hipFree(Bt);
-  (void)hipFree(C);
-  return 2.0 * size * (double)size * size / (ms * 1e9);
+  return time_256_tflops<unsigned char>(device, size, iters, 1,
+                                        (size_t)size * size / 2,  // nibble-packed
+                                        gemm_fp8_mx::fill_e2m1_hash_kernel,
+                                        {kernel})[0][0];
 }
 
 int device_count() {

@@ -40,6 +40,7 @@ def build_hipcore(force: bool = False) -> str:
     src = os.path.join(CSRC, "hipcore.hip")
     includes = [
         os.path.join(CSRC, "gemm_bf16.hip"),
+        os.path.join(CSRC, "gemm_8phase_common.h"),
         os.path.join(CSRC, "gemm_bf16_8phase.hip"),
         os.path.join(CSRC, "gemm_fp8_mx.hip"),
         os.path.join(CSRC, "hbm_memtest.hip"),

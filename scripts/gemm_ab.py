@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """8-phase GEMM variant A/B + race screen on a real MI355X (guide §5.4
-two-lane discipline: PIPE=1 is a new sync structure -> multi-run race screen
+two-lane discipline: phase-ahead (variants 2/3) is a new sync structure -> multi-run race screen
 at 256/512/4096 + within-probe interleaved A/B vs the unmodified template)."""
 import json
 import os
