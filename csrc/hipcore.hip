@@ -210,7 +210,9 @@ __global__ void fill_bf16_hash_kernel(__hip_bfloat16* p, size_t n, unsigned seed
     h *= 2246822519u;
     h ^= h >> 13;
     float v = ((h & 0xFFFFFF) / 8388608.0f) - 1.0f;  // [-1, 1)
-    p[i] = __hip_bfloat16(v);
+    // the bf16 rounding takes v >= 1 - 2^-9 up to 1.0 (one value in 1024):
+    // hold those at the largest bf16 below 1 so the fill stays in [-1, 1)
+    p[i] = __hip_bfloat16(fminf(v, 0.99609375f));
   }
 }
 
@@ -566,6 +568,16 @@ torch::Tensor gemm_bf16_bt(torch::Tensor A, torch::Tensor Bt, int swizzle,
 template <typename T>
 using GemmLaunch = std::function<void(hipStream_t, const T*, const T*, float*)>;
 
+// The one launch of a probe operand fill, shared by time_gemm_tflops and the
+// probe_fill binding so the fills that are tested are the fills that are timed.
+constexpr unsigned kProbeSeedA = 1u, kProbeSeedBt = 7u;
+
+template <typename T>
+void launch_probe_fill(void (*fill)(T*, size_t, unsigned), T* p, size_t n,
+                       unsigned seed, hipStream_t s) {
+  hipLaunchKernelGGL(fill, dim3(4096), dim3(256), 0, s, p, n, seed);
+}
+
 // One size^3 throughput measurement, shared by every *_tflops / _ab driver:
 // MFMA warm-up, three owned device buffers (released on any exit), hash-filled
 // operands, then each of `launches` timed once per round, round-robin.
@@ -579,8 +591,8 @@ std::vector<std::vector<double>> time_gemm_tflops(
   mfma_warmup(device, 20000);
   DeviceBuf<T> A(device, operand_elems), Bt(device, operand_elems);
   DeviceBuf<float> C(device, (size_t)size * size);
-  hipLaunchKernelGGL(fill, dim3(4096), dim3(256), 0, 0, A.ptr, operand_elems, 1u);
-  hipLaunchKernelGGL(fill, dim3(4096), dim3(256), 0, 0, Bt.ptr, operand_elems, 7u);
+  launch_probe_fill(fill, A.ptr, operand_elems, kProbeSeedA, 0);
+  launch_probe_fill(fill, Bt.ptr, operand_elems, kProbeSeedBt, 0);
   HIP_CHECK(hipDeviceSynchronize());
   std::vector<std::vector<double>> tf(rounds);
   for (auto& round : tf) {
@@ -831,6 +843,30 @@ double gemm_fp4_mx_tflops(int device, int size, int iters, int shape) {
                                         {kernel})[0][0];
 }
 
+// The operand fill of the *_tflops probes as a tensor of `n` stored elements
+// on the current device: "bf16" -> bfloat16, "e4m3" -> uint8 codes, "e2m1" ->
+// uint8 nibble pairs. Seeds 1 and 7 give the probes' A and Bt.
+torch::Tensor probe_fill(const std::string& kind, int64_t n, unsigned seed) {
+  TORCH_CHECK(n >= 0, "n must not be negative");
+  auto opts = torch::TensorOptions().device(torch::kCUDA);
+  auto stream = at::hip::getCurrentHIPStream();
+  if (kind == "bf16") {
+    auto t = torch::empty({n}, opts.dtype(torch::kBFloat16));
+    launch_probe_fill(fill_bf16_hash_kernel,
+                      reinterpret_cast<__hip_bfloat16*>(t.data_ptr()), (size_t)n,
+                      seed, stream.stream());
+    return t;
+  }
+  TORCH_CHECK(kind == "e4m3" || kind == "e2m1", "unknown fill kind ", kind,
+              " (bf16, e4m3, e2m1)");
+  auto t = torch::empty({n}, opts.dtype(torch::kUInt8));
+  launch_probe_fill(kind == "e4m3" ? gemm_fp8_mx::fill_e4m3_hash_kernel
+                                   : gemm_fp8_mx::fill_e2m1_hash_kernel,
+                    reinterpret_cast<unsigned char*>(t.data_ptr()), (size_t)n, seed,
+                    stream.stream());
+  return t;
+}
+
 int device_count() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -860,6 +896,7 @@ py::dict device_info(int device) {
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X native core: bandwidth probes + MFMA tiles";
+  m.def("probe_fill", &probe_fill, py::arg("kind"), py::arg("n"), py::arg("seed"));
   m.def("device_count", &device_count);
   m.def("device_info", &device_info, py::arg("device"));
   m.def("copy_f32", &copy_f32, py::arg("dst"), py::arg("src"));

@@ -90,7 +90,7 @@ EXACT_SETS = {
     "f32": {"max": 127.0 / 16.0, "granule": 1.0 / 16.0, "k_max": 1040},
     "e4m3": {"max": 7.5, "granule": 2.0 ** -4, "k_max": 1165},
     # all 16 codes: multiples of 0.5 up to 6
-    "e2m1": {"max": 6.0, "granule": 0.5, "k_max": 1280},
+    "e2m1": {"max": 6.0, "granule": 0.5, "k_max": 2048},
 }
 
 
@@ -182,6 +182,105 @@ def all_e2m1(rows: int, K: int, seed: int):
     return torch.from_numpy(pack_e2m1(nib)), torch.from_numpy(E2M1_LUT[nib])
 
 
+# ---------------------------------------------------------------------------
+# numpy ports of the probe operand fills (fill_bf16_hash_kernel in
+# csrc/hipcore.hip, fill_e4m3_hash_kernel and fill_e2m1_hash_kernel in
+# csrc/gemm_fp8_mx.hip): unsigned 32-bit arithmetic carried in uint64 and
+# masked, so nothing depends on numpy's overflow behaviour.
+# ---------------------------------------------------------------------------
+
+_U32 = np.uint64(0xFFFFFFFF)
+PROBE_SEEDS = (1, 7)  # A and Bt of every *_tflops probe
+BF16_BELOW_ONE = 1.0 - 2.0 ** -8  # the largest bf16 below 1
+
+
+def _u64(x: int) -> np.uint64:
+    return np.uint64(x)
+
+
+def f32_to_bf16_bits(v: np.ndarray) -> np.ndarray:
+    """Round-to-nearest-even float32 -> bf16 bit patterns (finite inputs)."""
+    b = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    return ((b + _u64(0x7FFF) + ((b >> _u64(16)) & _u64(1))) >> _u64(16)).astype(np.uint16)
+
+
+def bf16_bits_to_f64(bits: np.ndarray) -> np.ndarray:
+    return (bits.astype(np.uint32) << np.uint32(16)).view(np.float32).astype(np.float64)
+
+
+def fill_bf16_hash(n: int, seed: int) -> np.ndarray:
+    """bf16 bit patterns (uint16) of fill_bf16_hash_kernel."""
+    i = np.arange(n, dtype=np.uint64)
+    h = (i * _u64(2654435761) + _u64(seed)) & _U32
+    h ^= h >> _u64(15)
+    h = (h * _u64(2246822519)) & _U32
+    h ^= h >> _u64(13)
+    # every step is exact in float32: a 24-bit integer, a power-of-two
+    # division, and a difference of magnitude at most 1 on a 2^-23 grid
+    v = (h & _u64(0xFFFFFF)).astype(np.float32) / np.float32(8388608.0) - np.float32(1.0)
+    return f32_to_bf16_bits(np.minimum(v, np.float32(BF16_BELOW_ONE)))
+
+
+def _mx_hash(n: int, seed: int) -> np.ndarray:
+    i = np.arange(n, dtype=np.uint64)
+    h = ((i * _u64(2654435761)) & _U32) ^ _u64(seed)
+    h ^= h >> _u64(13)
+    h = (h * _u64(0x85EBCA6B)) & _U32
+    h ^= h >> _u64(16)
+    return h
+
+
+def fill_e4m3_hash(n: int, seed: int) -> np.ndarray:
+    """e4m3 codes (uint8) of fill_e4m3_hash_kernel: sign = hash bit 0,
+    exponent field 4 + bits 3:1, mantissa = bits 6:4."""
+    h = _mx_hash(n, seed)
+    return (((h & _u64(1)) << _u64(7)) | ((((h >> _u64(1)) & _u64(7)) + _u64(4)) << _u64(3))
+            | ((h >> _u64(4)) & _u64(7))).astype(np.uint8)
+
+
+def fill_e2m1_hash(n: int, seed: int) -> np.ndarray:
+    """Packed e2m1 bytes (uint8) of fill_e2m1_hash_kernel: hash bits 7:0."""
+    return (_mx_hash(n, seed) & _u64(0xFF)).astype(np.uint8)
+
+
+FILL_PORTS = {"bf16": fill_bf16_hash, "e4m3": fill_e4m3_hash, "e2m1": fill_e2m1_hash}
+
+
+def unpack_e2m1(packed: np.ndarray) -> np.ndarray:
+    """[rows][K/2] bytes -> [rows][K] nibble codes; inverse of pack_e2m1."""
+    out = np.empty((packed.shape[0], packed.shape[1] * 2), dtype=np.uint8)
+    out[:, 0::2] = packed & 0xF
+    out[:, 1::2] = packed >> 4
+    return out
+
+
+def check_fill_properties(kind: str, seed_a: np.ndarray, seed_b: np.ndarray) -> None:
+    """What a probe fill must be for the TF it feeds to mean anything (zero,
+    constant or sign-stuck operands inflate it). `seed_a` and `seed_b` are
+    the raw fills of one kind and length from the two probe seeds; the same
+    assertions run on the port and on the kernel's output."""
+    assert seed_a.shape == seed_b.shape and seed_a.size >= 1 << 20
+    for raw in (seed_a, seed_b):
+        # everything below is read off the histogram of the raw patterns
+        hist = np.bincount(raw, minlength=1 << (8 * raw.dtype.itemsize))
+        used = np.flatnonzero(hist)
+        if kind == "bf16":
+            v = bf16_bits_to_f64(used.astype(np.uint16))
+            assert v.min() >= -1.0 and v.max() < 1.0, (v.min(), v.max())
+            assert used.size > 1000, "bf16 fill is (nearly) constant"
+            neg = float(hist[0x8000:].sum()) / raw.size
+            assert abs(neg - 0.5) < 0.005, f"bf16 fill signs: {neg:.4f} negative"
+        elif kind == "e4m3":
+            assert not np.isin(used, E4M3_NAN_CODES).any()
+            assert sorted(set(((used >> 3) & 0xF).tolist())) == list(range(4, 12))
+            assert sorted(set((used >> 7).tolist())) == [0, 1]
+            assert sorted(set((used & 7).tolist())) == list(range(8))
+        else:
+            assert used.size == 256
+    differ = float(np.mean(seed_a != seed_b))
+    assert differ > 0.90, f"{kind} fills of the two seeds differ in {differ:.4f} of positions"
+
+
 def reference(a64: torch.Tensor, b64: torch.Tensor) -> torch.Tensor:
     """ref[M][N] = A64[M][K] @ B64[N][K].T in float64 on the CPU."""
     assert a64.dtype == torch.float64 and b64.dtype == torch.float64
@@ -204,6 +303,52 @@ def locate(row: int, col: int) -> dict:
     }
 
 
+NXCD = 8  # gemm_8ph::NXCD
+
+
+def _xcd_start(x: int, nwg: int) -> int:
+    """First tile of the contiguous range tile_coord<1> gives to XCD x."""
+    q, r = divmod(nwg, NXCD)
+    return x * (q + 1) if x < r else r * (q + 1) + (x - r) * q
+
+
+def block_tile(bid: int, tiles_n: int, nwg: int, xcd_remap: bool):
+    """(tile_row, tile_col) computed by workgroup `bid` of `nwg`: the formula
+    of tile_coord in csrc/gemm_8phase_common.h."""
+    if xcd_remap:
+        xcd, seq = bid % NXCD, bid // NXCD
+        bid = _xcd_start(xcd, nwg) + seq
+    return bid // tiles_n, bid % tiles_n
+
+
+def owner_block(tile_row: int, tile_col: int, tiles_n: int, nwg: int,
+                xcd_remap: bool):
+    """(blockIdx.x, blockIdx.x % 8) of the workgroup that computes a tile:
+    the inverse of block_tile. The second value is the XCD the workgroup runs
+    on under round-robin dispatch."""
+    t = tile_row * tiles_n + tile_col
+    assert 0 <= tile_col < tiles_n and 0 <= t < nwg, (tile_row, tile_col, tiles_n, nwg)
+    bid = t
+    if xcd_remap:
+        xcd = max(x for x in range(NXCD) if _xcd_start(x, nwg) <= t)
+        bid = (t - _xcd_start(xcd, nwg)) * NXCD + xcd
+    return bid, bid % NXCD
+
+
+def describe_owners(e: "KernelMismatch", tiles_n: int, nwg: int,
+                    xcd_remap: bool) -> str:
+    """Who computed what a KernelMismatch found bad: the block of the first
+    bad element, and the blockIdx % 8 classes of all bad tiles. One class
+    points at the hardware (an XCD); a pattern in tile coordinates at the
+    kernel."""
+    bid, xcd = owner_block(*e.where["tile"], tiles_n, nwg, xcd_remap)
+    classes = sorted({owner_block(tr, tc, tiles_n, nwg, xcd_remap)[1]
+                      for tr, tc in e.bad_tiles})
+    return (f"first bad element computed by blockIdx.x {bid} of {nwg} "
+            f"(blockIdx % 8 = {xcd}, xcd_remap={int(bool(xcd_remap))}); "
+            f"{len(e.bad_tiles)} bad tiles, their blockIdx % 8 in {classes}")
+
+
 class KernelMismatch(AssertionError):
     """Raised by the comparators; carries the location of the first bad
     element so tests (and people) can read off the phase or fragment."""
@@ -219,6 +364,7 @@ class KernelMismatch(AssertionError):
         cols = idx[:, 1]
         self.bad_rows = (int(rows.min()), int(rows.max()))
         self.bad_cols = (int(cols.min()), int(cols.max()))
+        self.bad_tiles = [tuple(t) for t in torch.unique(idx // TILE, dim=0).tolist()]
         r, c = self.first
         w = self.where
         msg = (

@@ -323,3 +323,179 @@ def test_mx_truncation_term_bounds_the_model_and_exact_set_is_untouched():
     ea, a = kr.exact_e4m3(64, 256, seed=43)
     eb, b = kr.exact_e4m3(96, 256, seed=44)
     assert torch.equal(kr.mx_fp8_truncated_reference(ea, eb), kr.reference(a, b))
+
+
+# ---------------------------------------------------------------------------
+# workgroup -> tile map (tile_coord in csrc/gemm_8phase_common.h)
+# ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("xcd_remap", [False, True])
+def test_block_to_tile_map_is_a_bijection_for_every_grid_size(xcd_remap):
+    """Every nwg in 1..2048: the blocks cover tiles 0..nwg-1 exactly once
+    (tiles_n = 1 makes the tile row the linear tile index), and owner_block
+    inverts block_tile."""
+    for nwg in range(1, 2049):
+        tiles = [kr.block_tile(b, 1, nwg, xcd_remap)[0] for b in range(nwg)]
+        assert sorted(tiles) == list(range(nwg)), (nwg, xcd_remap)
+        if nwg in (1, 7, 8, 9, 16, 306, 2047, 2048):
+            for b, t in enumerate(tiles):
+                assert kr.owner_block(t, 0, 1, nwg, xcd_remap) == (b, b % 8)
+
+
+def test_owner_block_spot_values():
+    # without the remap a block computes the tile of its own index
+    assert kr.owner_block(2, 1, 3, 9, False) == (7, 7)
+    assert kr.owner_block(16, 17, 18, 306, False) == (305, 1)
+    # nwg = 9 (q = 1, r = 1): XCD 0 gets tiles 0, 1; XCD x > 0 gets tile x + 1
+    assert [kr.block_tile(b, 3, 9, True) for b in range(9)] == [
+        (0, 0), (0, 2), (1, 0), (1, 1), (1, 2), (2, 0), (2, 1), (2, 2), (0, 1)]
+    assert kr.owner_block(0, 1, 3, 9, True) == (8, 0)
+    assert kr.owner_block(2, 2, 3, 9, True) == (7, 7)
+    # nwg = 16 (q = 2, r = 0): XCD x gets tiles 2x, 2x + 1
+    assert kr.owner_block(0, 1, 4, 16, True) == (8, 0)
+    assert kr.owner_block(3, 3, 4, 16, True) == (15, 7)
+    assert kr.owner_block(1, 2, 4, 16, True) == (3, 3)
+    # nwg = 306 (q = 38, r = 2): XCDs 0, 1 get 39 tiles, the others 38
+    assert kr.owner_block(0, 0, 18, 306, True) == (0, 0)
+    assert kr.owner_block(2, 2, 18, 306, True) == (38 * 8, 0)      # tile 38, last of XCD 0
+    assert kr.owner_block(2, 3, 18, 306, True) == (1, 1)           # tile 39, first of XCD 1
+    assert kr.owner_block(4, 5, 18, 306, True) == (38 * 8 + 1, 1)  # tile 77, last of XCD 1
+    assert kr.owner_block(4, 6, 18, 306, True) == (2, 2)           # tile 78, first of XCD 2
+    assert kr.owner_block(16, 17, 18, 306, True) == (37 * 8 + 7, 7)  # the last tile
+    # blocks 304, 305 are the 39th of XCDs 0 and 1; no block beyond them
+    assert kr.block_tile(305, 18, 306, True) == (4, 5)
+    with pytest.raises(AssertionError):
+        kr.owner_block(17, 0, 18, 306, True)
+
+
+def test_mismatch_message_names_the_owning_block(problem):
+    a, b, ref, good = problem  # 512 x 768: 2 x 3 tiles, nwg = 6
+    C = good.clone()
+    C[300, 517] += 1.0 / 256.0  # tile (1, 2) = tile 5
+    C[10, 300] += 1.0 / 256.0   # tile (0, 1) = tile 1
+    with pytest.raises(kr.KernelMismatch) as ei:
+        kr.assert_exact(C, ref)
+    e = ei.value
+    assert e.bad_tiles == [(0, 1), (1, 2)]
+    text = kr.describe_owners(e, 3, 6, True)
+    assert "blockIdx.x 1 of 6 (blockIdx % 8 = 1, xcd_remap=1)" in text
+    assert "2 bad tiles, their blockIdx % 8 in [1, 5]" in text
+
+
+# ---------------------------------------------------------------------------
+# the full-machine shapes and their exactness
+# ---------------------------------------------------------------------------
+
+def test_full_machine_shapes_and_k():
+    import test_gpu_kernels_full as full
+
+    s = full.full_shapes(256)
+    assert s == {"one-per-cu": (16, 16), "second-round": (17, 18)}
+    assert divmod(16 * 16, 8) == (32, 0) and divmod(17 * 18, 8) == (38, 2)
+    for cus in (64, 104, 228, 256, 304):
+        s = full.full_shapes(cus)
+        one, two = s["one-per-cu"], s["second-round"]
+        assert one[0] * one[1] == cus
+        assert two[0] * two[1] > cus and (two[0] * two[1]) % 8 >= 2
+    for kind, K in full.K_FULL.items():
+        kr.require_exact(kind, K)
+    # 19 kernels x (2 idle shapes + 1 contended), ordered so that the cases
+    # of one problem are neighbours (full_problem keeps only the latest)
+    assert len(full.CASES) == 19 * 3
+    keys = [c[:2] for c in full.CASES]
+    assert len({k for k in keys}) == sum(a != b for a, b in zip(keys, keys[1:])) + 1
+    # no operand fits one XCD's 4 MiB of L2 next to the other (bytes per row:
+    # bf16 2K, fp8 K, fp4 K/2; the smallest is fp4 at exactly 4 MiB)
+    assert 4096 * min(1024 * 2, 1152, 2048 // 2) >= 4 << 20
+
+
+# ---------------------------------------------------------------------------
+# numpy ports of the probe fills
+# ---------------------------------------------------------------------------
+
+FILL_N = 1 << 20
+
+
+def test_bf16_rounding_port_matches_torch():
+    g = torch.Generator().manual_seed(5)
+    v = torch.cat([torch.rand(4096, generator=g) * 2 - 1,
+                   torch.tensor([1 - 2.0 ** -9, 1 - 2.0 ** -9 - 2.0 ** -20, 1 - 2.0 ** -8,
+                                 0.0, -1.0, 2.0 ** -9 + 2.0 ** -17])])
+    want = v.to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    bits = kr.f32_to_bf16_bits(v.numpy())
+    assert np.array_equal(bits, want)
+    assert np.array_equal(kr.bf16_bits_to_f64(bits), v.to(torch.bfloat16).double().numpy())
+
+
+def test_fill_ports_first_values_by_hand():
+    """Element 0 and 1 of each port, worked through the C expressions with
+    Python integers."""
+    def bf16(i, seed):
+        h = (i * 2654435761 + seed) & 0xFFFFFFFF
+        h ^= h >> 15
+        h = (h * 2246822519) & 0xFFFFFFFF
+        h ^= h >> 13
+        v = min((h & 0xFFFFFF) / 8388608.0 - 1.0, kr.BF16_BELOW_ONE)
+        return int(torch.tensor(v, dtype=torch.float32).to(torch.bfloat16)
+                   .view(torch.int16).item()) & 0xFFFF
+
+    def mx(i, seed):
+        h = ((i * 2654435761) & 0xFFFFFFFF) ^ seed
+        h ^= h >> 13
+        h = (h * 0x85EBCA6B) & 0xFFFFFFFF
+        return h ^ (h >> 16)
+
+    for seed in kr.PROBE_SEEDS:
+        idx = [0, 1, 2, FILL_N // 2, FILL_N - 1]
+        assert [int(kr.fill_bf16_hash(FILL_N, seed)[i]) for i in idx] == \
+            [bf16(i, seed) for i in idx]
+        assert [int(kr.fill_e2m1_hash(FILL_N, seed)[i]) for i in idx] == \
+            [mx(i, seed) & 0xFF for i in idx]
+        assert [int(kr.fill_e4m3_hash(FILL_N, seed)[i]) for i in idx] == \
+            [((mx(i, seed) & 1) << 7) | ((((mx(i, seed) >> 1) & 7) + 4) << 3)
+             | ((mx(i, seed) >> 4) & 7) for i in idx]
+
+
+@pytest.mark.parametrize("kind", sorted(kr.FILL_PORTS))
+def test_fill_ports_have_the_properties_the_probes_need(kind):
+    a, b = (kr.FILL_PORTS[kind](FILL_N, s) for s in kr.PROBE_SEEDS)
+    assert a.dtype == (np.uint16 if kind == "bf16" else np.uint8)
+    kr.check_fill_properties(kind, a, b)
+    # a prefix of a longer fill is the shorter fill; an empty one is empty
+    assert np.array_equal(kr.FILL_PORTS[kind](1000, 7), b[:1000])
+    assert kr.FILL_PORTS[kind](0, 7).shape == (0,)
+
+
+def test_bf16_fill_is_held_below_one():
+    """Finding behind the fminf in fill_bf16_hash_kernel: the hash value lies
+    in [-1, 1) as a float, but one in 1024 of them is at least 1 - 2^-9 and
+    rounds to bf16 1.0. The clamp holds those at 1 - 2^-8."""
+    bits = kr.fill_bf16_hash(FILL_N, 1)
+    v = kr.bf16_bits_to_f64(bits)
+    top = float(np.mean(v == kr.BF16_BELOW_ONE))
+    # of the range of width 2: 2^-8 that round to it, 2^-9 that are clamped
+    assert abs(top - 1.5 * 2.0 ** -8 / 2) < 2e-4, top
+    assert v.max() == kr.BF16_BELOW_ONE and v.min() >= -1.0
+
+
+@pytest.mark.parametrize("kind", sorted(kr.FILL_PORTS))
+def test_fill_property_check_rejects_broken_fills(kind):
+    a, b = (kr.FILL_PORTS[kind](FILL_N, s) for s in kr.PROBE_SEEDS)
+    with pytest.raises(AssertionError, match="differ in"):
+        kr.check_fill_properties(kind, a, a.copy())  # seed ignored
+    broken = []
+    if kind == "bf16":
+        broken = [a & 0x7FFF,                                   # sign stuck
+                  np.where(np.arange(FILL_N) == 5, 0x3F80, a).astype(a.dtype),  # a 1.0
+                  np.zeros_like(a)]
+    elif kind == "e4m3":
+        broken = [a & 0x7F, a | 0x80,                           # sign stuck
+                  np.where(np.arange(FILL_N) == 5, 0x7F, a).astype(a.dtype),  # a NaN
+                  a & 0xF8,                                     # mantissa stuck
+                  np.where((a >> 3) & 0xF == 11, a - 8, a).astype(a.dtype),  # exponent 11 lost
+                  np.where(np.arange(FILL_N) == 5, 0x18, a).astype(a.dtype)]  # exponent 3
+    else:
+        broken = [a & 0x7F, a | 0x01, np.zeros_like(a)]
+    for bad in broken:
+        with pytest.raises(AssertionError):
+            kr.check_fill_properties(kind, bad, b)
