@@ -58,8 +58,8 @@
 // fill and first verify). They change values only, never an address; the
 // host rejects entries out of range and the kernel bounds the LDS word again.
 //
-// Included by hipcore.hip (needs HIP_CHECK, the torch headers and
-// hbm_memtest.hip's fmix32 and RAII guards).
+// Included by hipcore.hip (needs the torch headers, hip_host.h for HIP_CHECK
+// and the resource owners the driver holds, and hbm_memtest.hip's fmix32).
 
 namespace cu_check {
 
@@ -394,19 +394,11 @@ torch::Tensor cu_check_tile(const std::string& fmt, long long tile, u64 seed) {
   auto stream = at::hip::getCurrentHIPStream();
   float* p = out.data_ptr<float>();
   const u32 lo = (u32)seed, hi = (u32)(seed >> 32), t = (u32)tile;
-  switch (f) {
-    case kBf16:
-      hipLaunchKernelGGL(cu_check_tile_kernel<kBf16>, dim3(1), dim3(64), 0,
-                         stream.stream(), p, lo, hi, t);
-      break;
-    case kFp8:
-      hipLaunchKernelGGL(cu_check_tile_kernel<kFp8>, dim3(1), dim3(64), 0,
-                         stream.stream(), p, lo, hi, t);
-      break;
-    default:
-      hipLaunchKernelGGL(cu_check_tile_kernel<kFp4>, dim3(1), dim3(64), 0,
-                         stream.stream(), p, lo, hi, t);
-  }
+  constexpr void (*kTileKernels[3])(float*, u32, u32, u32) = {
+      cu_check_tile_kernel<kBf16>, cu_check_tile_kernel<kFp8>,
+      cu_check_tile_kernel<kFp4>};
+  hipLaunchKernelGGL(kTileKernels[f], dim3(1), dim3(64), 0, stream.stream(), p,
+                     lo, hi, t);
   HIP_CHECK(hipGetLastError());
   return out;
 }
@@ -465,15 +457,9 @@ inline u32 cu_key(u32 xcc, u32 hw_id) { return (xcc & 0xFu) << 8 | ((hw_id >> 8)
 
 DriverResult run_driver(int device, int rounds, u64 seed, int grid_mult,
                         const std::vector<Inject>& inject) {
-  using hbm_memtest::DeviceRestore;
-  using hbm_memtest::DevMem;
-  using hbm_memtest::EventGuard;
-  using hbm_memtest::StreamGuard;
   DriverResult out;
 
-  DeviceRestore restore;
-  HIP_CHECK(hipGetDevice(&restore.prev));
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope(device);
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, device));
   out.cus = prop.multiProcessorCount;
@@ -503,42 +489,38 @@ DriverResult run_driver(int device, int rounds, u64 seed, int grid_mult,
                                 hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)out.lds_bytes));
 
-  const size_t rec_bytes = (size_t)out.grid * kRecWords * sizeof(u32);
-  DevMem rec, inj;
-  HIP_CHECK(hipMalloc(&rec.ptr, rec_bytes));
+  const size_t rec_words = (size_t)out.grid * kRecWords;
+  const size_t rec_bytes = rec_words * sizeof(u32);
+  DeviceBuf<u32> rec(device, rec_words);
   std::vector<u32> inj_host;
   for (auto& in : inject) {
     const u32 e[kInjectWords] = {in.workgroup, in.test, in.index,
                                  in.lane_or_word, in.mask};
     inj_host.insert(inj_host.end(), e, e + kInjectWords);
   }
-  HIP_CHECK(hipMalloc(&inj.ptr, std::max<size_t>(inj_host.size(), 4) * sizeof(u32)));
+  DeviceBuf<u32> inj(device, std::max<size_t>(inj_host.size(), 4));
 
-  StreamGuard stream;
-  HIP_CHECK(hipStreamCreate(&stream.s));
-  EventGuard t0, t1;
-  HIP_CHECK(hipEventCreate(&t0.e));
-  HIP_CHECK(hipEventCreate(&t1.e));
+  Stream stream;
+  Event t0, t1;
   if (!inj_host.empty())
     HIP_CHECK(hipMemcpyAsync(inj.ptr, inj_host.data(),
                              inj_host.size() * sizeof(u32),
                              hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipEventRecord(t0.e, stream.s));
+  t0.record(stream);
 
-  std::vector<u32> host((size_t)out.grid * kRecWords);
+  std::vector<u32> host(rec_words);
   std::vector<bool> seen(1u << 12, false);
   int distinct = 0;
   // On an idle GPU the first launch covers every CU; a busy one may need more.
   while (out.launches < kMaxLaunches) {
     HIP_CHECK(hipMemsetAsync(rec.ptr, 0, rec_bytes, stream.s));
     hipLaunchKernelGGL(cu_check_kernel, dim3(out.grid), dim3(kThreads),
-                       out.lds_bytes, stream.s, static_cast<u32*>(rec.ptr),
-                       rounds, (u32)seed, (u32)(seed >> 32), lds_vecs,
-                       static_cast<const u32*>(inj.ptr), (int)inject.size());
+                       out.lds_bytes, stream.s, rec.ptr, rounds, (u32)seed,
+                       (u32)(seed >> 32), lds_vecs, inj.ptr, (int)inject.size());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(host.data(), rec.ptr, rec_bytes,
                              hipMemcpyDeviceToHost, stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));
+    stream.synchronize();
     ++out.launches;
     for (int g = 0; g < out.grid; ++g) {
       const u32* w = host.data() + (size_t)g * kRecWords;
@@ -554,11 +536,9 @@ DriverResult run_driver(int device, int rounds, u64 seed, int grid_mult,
     out.words.insert(out.words.end(), host.begin(), host.end());
     if (out.grid < out.cus || distinct >= out.cus) break;
   }
-  HIP_CHECK(hipEventRecord(t1.e, stream.s));
-  HIP_CHECK(hipEventSynchronize(t1.e));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
-  out.seconds = ms / 1e3;
+  t1.record(stream);
+  t1.synchronize();
+  out.seconds = Event::elapsed_ms(t0, t1) / 1e3;
   return out;
 }
 

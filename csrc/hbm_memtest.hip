@@ -31,7 +31,8 @@
 // a trailing odd word are handled word by word in the same launch. Every
 // index and byte offset is 64-bit.
 //
-// Included by hipcore.hip (needs HIP_CHECK and the torch headers).
+// Included by hipcore.hip (needs the torch headers, and hip_host.h for
+// HIP_CHECK and the resource owners the driver holds).
 
 namespace hbm_memtest {
 
@@ -248,26 +249,15 @@ __global__ __launch_bounds__(kBlock) void memtest_kernel(
   }
 }
 
-template <int MODE>
-void launch_mode(int pat, dim3 grid, hipStream_t s, u64* p, u64 n, u64 base,
-                 u64 seed, u64 inv, u64* rep, u64 cap) {
-  switch (pat) {
-    case kAddr:
-      hipLaunchKernelGGL((memtest_kernel<MODE, kAddr>), grid, dim3(kBlock), 0, s,
-                         p, n, base, seed, inv, rep, cap);
-      break;
-    case kRand:
-      hipLaunchKernelGGL((memtest_kernel<MODE, kRand>), grid, dim3(kBlock), 0, s,
-                         p, n, base, seed, inv, rep, cap);
-      break;
-    case kZero:
-      hipLaunchKernelGGL((memtest_kernel<MODE, kZero>), grid, dim3(kBlock), 0, s,
-                         p, n, base, seed, inv, rep, cap);
-      break;
-    default:
-      TORCH_CHECK(false, "unknown memtest pattern code ", pat);
-  }
-}
+// The instantiations as [mode][pattern].
+constexpr void (*kKernels[3][3])(u64*, u64, u64, u64, u64, u64*, u64) = {
+    {memtest_kernel<kWrite, kAddr>, memtest_kernel<kWrite, kRand>,
+     memtest_kernel<kWrite, kZero>},
+    {memtest_kernel<kVerify, kAddr>, memtest_kernel<kVerify, kRand>,
+     memtest_kernel<kVerify, kZero>},
+    {memtest_kernel<kVerifyFlip, kAddr>, memtest_kernel<kVerifyFlip, kRand>,
+     memtest_kernel<kVerifyFlip, kZero>},
+};
 
 // The one launch path, shared by the tensor bindings and the driver. rep may
 // be null for kWrite only.
@@ -282,19 +272,10 @@ void launch(int mode, int pat, u64* p, u64 n, u64 base, u64 seed, bool invert,
   const u64 ntiles = (nvec + kTileVecs - 1) / kTileVecs;
   dim3 grid((unsigned)std::min<u64>(std::max<u64>(ntiles, 1), kMaxGrid));
   const u64 inv = invert ? ~0ull : 0ull;
-  switch (mode) {
-    case kWrite:
-      launch_mode<kWrite>(pat, grid, s, p, n, base, seed, inv, rep, cap);
-      break;
-    case kVerify:
-      launch_mode<kVerify>(pat, grid, s, p, n, base, seed, inv, rep, cap);
-      break;
-    case kVerifyFlip:
-      launch_mode<kVerifyFlip>(pat, grid, s, p, n, base, seed, inv, rep, cap);
-      break;
-    default:
-      TORCH_CHECK(false, "unknown memtest mode ", mode);
-  }
+  TORCH_CHECK(mode >= 0 && mode < 3, "unknown memtest mode ", mode);
+  TORCH_CHECK(pat >= 0 && pat < 3, "unknown memtest pattern code ", pat);
+  hipLaunchKernelGGL(kKernels[mode][pat], grid, dim3(kBlock), 0, s, p, n, base,
+                     seed, inv, rep, cap);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -389,41 +370,9 @@ py::dict memtest_geometry() {
 }
 
 // ---------------------------------------------------------------------------
-// Driver: the burn-in pass over hipMalloc'd chunks
+// Driver: the burn-in pass over chunks of its own (DeviceBuf, never torch's
+// caching allocator)
 // ---------------------------------------------------------------------------
-
-struct DevMem {
-  void* ptr = nullptr;
-  DevMem() = default;
-  DevMem(const DevMem&) = delete;
-  DevMem& operator=(const DevMem&) = delete;
-  DevMem(DevMem&& o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
-  ~DevMem() {
-    if (ptr) (void)hipFree(ptr);
-  }
-};
-
-struct StreamGuard {
-  hipStream_t s = nullptr;
-  ~StreamGuard() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-
-struct EventGuard {
-  hipEvent_t e = nullptr;
-  ~EventGuard() {
-    if (e) (void)hipEventDestroy(e);
-  }
-};
-
-// Restores the caller's current device (torch keeps its own notion of it).
-struct DeviceRestore {
-  int prev = -1;
-  ~DeviceRestore() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 struct StepRecord {
   const char* step;
@@ -448,26 +397,16 @@ DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
     TORCH_CHECK(in.first < total_words, "inject: word ", in.first,
                 " is outside the ", total_words, " words under test");
 
-  DeviceRestore restore;
-  HIP_CHECK(hipGetDevice(&restore.prev));
-  HIP_CHECK(hipSetDevice(device));
-
-  std::vector<DevMem> chunks(chunk_words.size());
-  for (size_t i = 0; i < chunk_words.size(); ++i)
-    HIP_CHECK(hipMalloc(&chunks[i].ptr, chunk_words[i] * 8));
+  DeviceScope scope(device);
+  std::vector<DeviceBuf<u64>> chunks;
+  for (u64 w : chunk_words) chunks.emplace_back(device, w);
   const size_t rep_words = kRepHeader + 3 * cap;
-  DevMem rep;
-  HIP_CHECK(hipMalloc(&rep.ptr, rep_words * 8));
+  DeviceBuf<u64> rep(device, rep_words);
   std::vector<u64> host_rep(rep_words);
 
-  StreamGuard stream;
-  HIP_CHECK(hipStreamCreate(&stream.s));
-  EventGuard t0, t1, w0, w1;
-  HIP_CHECK(hipEventCreate(&t0.e));
-  HIP_CHECK(hipEventCreate(&t1.e));
-  HIP_CHECK(hipEventCreate(&w0.e));
-  HIP_CHECK(hipEventCreate(&w1.e));
-  HIP_CHECK(hipEventRecord(w0.e, stream.s));
+  Stream stream;
+  Event t0, t1, w0, w1;
+  w0.record(stream);
 
   // One step = one mode over ALL chunks: with >= 1 GiB under test every line
   // has left the 256 MiB Infinity Cache before the next step reads it, so
@@ -475,20 +414,19 @@ DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
   auto step = [&](const char* name, int mode, int pat, bool invert) {
     if (mode != kWrite)
       HIP_CHECK(hipMemsetAsync(rep.ptr, 0, rep_words * 8, stream.s));
-    HIP_CHECK(hipEventRecord(t0.e, stream.s));
+    t0.record(stream);
     u64 g = 0;
     for (size_t i = 0; i < chunks.size(); ++i) {
-      launch(mode, pat, static_cast<u64*>(chunks[i].ptr), chunk_words[i], g,
-             seed, invert, static_cast<u64*>(rep.ptr), cap, stream.s);
+      launch(mode, pat, chunks[i].ptr, chunk_words[i], g, seed, invert, rep.ptr,
+             cap, stream.s);
       g += chunk_words[i];
     }
-    HIP_CHECK(hipEventRecord(t1.e, stream.s));
+    t1.record(stream);
     if (mode != kWrite)
       HIP_CHECK(hipMemcpyAsync(host_rep.data(), rep.ptr, rep_words * 8,
                                hipMemcpyDeviceToHost, stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
+    stream.synchronize();
+    const float ms = Event::elapsed_ms(t0, t1);
     ++out.passes;
     if (mode == kWrite) {
       if (pat != kZero) out.write_ms += ms;
@@ -510,7 +448,7 @@ DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
     u64 g = in.first, off = 0;
     size_t c = 0;
     while (g - off >= chunk_words[c]) off += chunk_words[c++];
-    u64* addr = static_cast<u64*>(chunks[c].ptr) + (g - off);
+    u64* addr = chunks[c].ptr + (g - off);
     u64 word = 0;
     HIP_CHECK(hipMemcpy(&word, addr, 8, hipMemcpyDeviceToHost));
     word ^= in.second;
@@ -523,11 +461,9 @@ DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
   step("verify rand inverted", kVerify, kRand, true);
   if (scrub) step("scrub", kWrite, kZero, false);
 
-  HIP_CHECK(hipEventRecord(w1.e, stream.s));
-  HIP_CHECK(hipEventSynchronize(w1.e));
-  float wall = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&wall, w0.e, w1.e));
-  out.seconds = wall / 1e3;
+  w1.record(stream);
+  w1.synchronize();
+  out.seconds = Event::elapsed_ms(w0, w1) / 1e3;
   return out;
 }
 

@@ -31,14 +31,12 @@
 #include <string>
 #include <vector>
 
-#define HIP_CHECK(expr)                                                        \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      throw std::runtime_error(std::string(#expr) + " failed: " +              \
-                               hipGetErrorString(_e));                         \
-    }                                                                          \
-  } while (0)
+#include "hip_host.h"
+
+using hip_host::DeviceBuf;
+using hip_host::DeviceScope;
+using hip_host::Event;
+using hip_host::Stream;
 
 namespace {
 
@@ -220,125 +218,101 @@ __global__ void fill_bf16_hash_kernel(__hip_bfloat16* p, size_t n, unsigned seed
 // Host-side probe machinery
 // ---------------------------------------------------------------------------
 
-// Owns `count` elements of device memory on `device`.
-template <typename T>
-struct DeviceBuf {
-  T* ptr = nullptr;
-  int device;
-  DeviceBuf(int device, size_t count) : device(device) {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipMalloc(&ptr, count * sizeof(T)));
-  }
-  DeviceBuf(const DeviceBuf&) = delete;
-  DeviceBuf& operator=(const DeviceBuf&) = delete;
-  ~DeviceBuf() {
-    if (ptr) {
-      (void)hipSetDevice(device);
-      (void)hipFree(ptr);
-    }
-  }
-};
+// Every probe below makes its device current through a DeviceScope, so the
+// calling thread leaves on the device it came in on.
 
 double time_kernel_ms(int device, std::function<void(hipStream_t)> body,
                       int iters) {
-  HIP_CHECK(hipSetDevice(device));
-  hipStream_t stream;
-  HIP_CHECK(hipStreamCreate(&stream));
-  hipEvent_t t0, t1;
-  HIP_CHECK(hipEventCreate(&t0));
-  HIP_CHECK(hipEventCreate(&t1));
-  body(stream);  // one warm launch
-  HIP_CHECK(hipStreamSynchronize(stream));
-  HIP_CHECK(hipEventRecord(t0, stream));
-  for (int i = 0; i < iters; ++i) body(stream);
-  HIP_CHECK(hipEventRecord(t1, stream));
-  HIP_CHECK(hipEventSynchronize(t1));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-  HIP_CHECK(hipEventDestroy(t0));
-  HIP_CHECK(hipEventDestroy(t1));
-  HIP_CHECK(hipStreamDestroy(stream));
-  return ms / iters;
+  DeviceScope scope(device);
+  Stream stream;
+  Event t0, t1;
+  body(stream.s);  // one warm launch
+  stream.synchronize();
+  t0.record(stream);
+  for (int i = 0; i < iters; ++i) body(stream.s);
+  t1.record(stream);
+  t1.synchronize();
+  return Event::elapsed_ms(t0, t1) / iters;
 }
 
 void mfma_warmup(int device, int spins) {
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope(device);
   hipLaunchKernelGGL(mfma_warmup_kernel, dim3(2048), dim3(256), 0, 0, nullptr,
                      spins);
   HIP_CHECK(hipDeviceSynchronize());
 }
 
+// The `mib` MiB of floats a bandwidth probe moves.
+size_t probe_floats(int mib) { return (size_t)mib * 1024 * 1024 / sizeof(float); }
+
+// A probe's source buffer: `n` floats on `device`, every byte set to 1.
+DeviceBuf<float> probe_source(int device, size_t n) {
+  DeviceBuf<float> src(device, n);
+  DeviceScope scope(device);
+  HIP_CHECK(hipMemset(src.ptr, 1, n * sizeof(float)));
+  return src;
+}
+
+// Enables peer access from `dst` to `src` and says whether a kernel on `dst`
+// may read `src`'s memory: false when the devices are not peers or when
+// enabling fails, and then the pair is timed on the copy engine.
+bool enable_peer_read(int dst, int src) {
+  if (dst == src) return true;
+  int can = 0;
+  HIP_CHECK(hipDeviceCanAccessPeer(&can, dst, src));
+  if (!can) return false;
+  DeviceScope scope(dst);
+  hipError_t e = hipDeviceEnablePeerAccess(src, 0);
+  (void)hipGetLastError();  // "already enabled" is sticky otherwise
+  return e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled;
+}
+
+// GB/s of `n` floats from `src` on src_dev to `dst` on dst_dev, timed on
+// dst_dev. kernel_path: the float4 copy kernel; on one device that is the HBM
+// stream and read + write bytes count, across devices it pulls over xGMI
+// (per-link peak ≈153 GB/s, 7 links/GPU on an 8-GPU node) and the bytes count
+// once. Otherwise hipMemcpyPeerAsync, the SDMA/blit path (on one device that
+// is the plain device-to-device hipMemcpyAsync).
+double time_pair_gbps(int src_dev, const float* src, int dst_dev, float* dst,
+                      size_t n, bool kernel_path, int iters) {
+  const size_t bytes = n * sizeof(float);
+  std::function<void(hipStream_t)> body;
+  if (kernel_path) {
+    body = [=](hipStream_t s) { launch_copy_f32(src, dst, n, s); };
+  } else {
+    body = [=](hipStream_t s) {
+      HIP_CHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, s));
+    };
+  }
+  double ms = time_kernel_ms(dst_dev, body, iters);
+  return (src_dev == dst_dev ? 2.0 : 1.0) * bytes / (ms * 1e6);
+}
+
+// One pair with buffers of its own. warm: MFMA clock ramp on dst_dev first.
+double pair_bandwidth_gbps(int src_dev, int dst_dev, int mib, int iters,
+                           bool kernel_path, bool warm) {
+  const size_t n = probe_floats(mib);
+  if (warm) mfma_warmup(dst_dev, 2000);
+  DeviceBuf<float> src = probe_source(src_dev, n), dst(dst_dev, n);
+  return time_pair_gbps(src_dev, src.ptr, dst_dev, dst.ptr, n, kernel_path, iters);
+}
+
 // Local HBM stream bandwidth: copy of `mib` MiB on one device; GB/s counts
 // read + write bytes (achievable ceiling ≈6.3 TB/s on MI355X).
 double stream_bandwidth_gbps(int device, int mib, int iters) {
-  size_t n = (size_t)mib * 1024 * 1024 / sizeof(float);
-  HIP_CHECK(hipSetDevice(device));
-  mfma_warmup(device, 2000);
-  DeviceBuf<float> src(device, n), dst(device, n);
-  HIP_CHECK(hipMemset(src.ptr, 1, n * sizeof(float)));
-  double ms = time_kernel_ms(
-      device,
-      [&](hipStream_t s) { launch_copy_f32(src.ptr, dst.ptr, n, s); }, iters);
-  return (2.0 * n * sizeof(float)) / (ms * 1e6);
+  return pair_bandwidth_gbps(device, device, mib, iters, true, true);
 }
 
-// Reference point: SDMA/blit path via hipMemcpyAsync DtoD on one device.
+// Reference point: the SDMA/blit path on one device.
 double memcpy_bandwidth_gbps(int device, int mib, int iters) {
-  size_t n = (size_t)mib * 1024 * 1024 / sizeof(float);
-  HIP_CHECK(hipSetDevice(device));
-  DeviceBuf<float> src(device, n), dst(device, n);
-  HIP_CHECK(hipMemset(src.ptr, 1, n * sizeof(float)));
-  double ms = time_kernel_ms(
-      device,
-      [&](hipStream_t s) {
-        HIP_CHECK(hipMemcpyAsync(dst.ptr, src.ptr, n * sizeof(float),
-                                 hipMemcpyDeviceToDevice, s));
-      },
-      iters);
-  return (2.0 * n * sizeof(float)) / (ms * 1e6);
+  return pair_bandwidth_gbps(device, device, mib, iters, false, false);
 }
 
-// Peer bandwidth: dst-device kernel pulls from src-device memory (remote
-// reads ride xGMI; per-link peak ≈153 GB/s, 7 links/GPU on an 8-GPU node).
-// Falls back to hipMemcpyPeerAsync (SDMA path) when kernel p2p access is
-// not available.
+// Peer bandwidth: dst-device kernel pulls from src-device memory, or the copy
+// engine where kernel p2p access is not available.
 double p2p_bandwidth_gbps(int src_dev, int dst_dev, int mib, int iters) {
-  if (src_dev == dst_dev) return stream_bandwidth_gbps(src_dev, mib, iters);
-  size_t n = (size_t)mib * 1024 * 1024 / sizeof(float);
-
-  int can_access = 0;
-  HIP_CHECK(hipDeviceCanAccessPeer(&can_access, dst_dev, src_dev));
-
-  DeviceBuf<float> src(src_dev, n);
-  HIP_CHECK(hipMemset(src.ptr, 1, n * sizeof(float)));
-  DeviceBuf<float> dst(dst_dev, n);
-
-  if (can_access) {
-    hipError_t e = hipDeviceEnablePeerAccess(src_dev, 0);
-    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) {
-      (void)hipGetLastError();
-      can_access = 0;
-    } else {
-      (void)hipGetLastError();
-    }
-  }
-  mfma_warmup(dst_dev, 2000);
-  double ms;
-  if (can_access) {
-    ms = time_kernel_ms(
-        dst_dev,
-        [&](hipStream_t s) { launch_copy_f32(src.ptr, dst.ptr, n, s); }, iters);
-  } else {
-    ms = time_kernel_ms(
-        dst_dev,
-        [&](hipStream_t s) {
-          HIP_CHECK(hipMemcpyPeerAsync(dst.ptr, dst_dev, src.ptr, src_dev,
-                                       n * sizeof(float), s));
-        },
-        iters);
-  }
-  // count bytes moved over the link once (n*4), not read+write
-  return (double)(n * sizeof(float)) / (ms * 1e6);
+  return pair_bandwidth_gbps(src_dev, dst_dev, mib, iters,
+                             enable_peer_read(dst_dev, src_dev), true);
 }
 
 // Full pairwise matrix in one call: per-device src/dst buffers allocated
@@ -349,63 +323,21 @@ std::vector<std::vector<double>> p2p_matrix(int mib, int iters) {
   int n = 0;
   HIP_CHECK(hipGetDeviceCount(&n));
   std::vector<std::vector<double>> out(n, std::vector<double>(n, 0.0));
-  if (n == 0) return out;
-  size_t count = (size_t)mib * 1024 * 1024 / sizeof(float);
+  const size_t count = probe_floats(mib);
 
-  std::vector<float*> src(n, nullptr), dst(n, nullptr);
+  std::vector<DeviceBuf<float>> src, dst;
+  // readable[d][s]: a kernel on d may read s's memory
+  std::vector<std::vector<bool>> readable(n, std::vector<bool>(n, false));
   for (int i = 0; i < n; ++i) {
-    HIP_CHECK(hipSetDevice(i));
-    HIP_CHECK(hipMalloc(&src[i], count * sizeof(float)));
-    HIP_CHECK(hipMalloc(&dst[i], count * sizeof(float)));
-    HIP_CHECK(hipMemset(src[i], 1, count * sizeof(float)));
+    src.push_back(probe_source(i, count));
+    dst.emplace_back(i, count);
     mfma_warmup(i, 2000);
-    for (int j = 0; j < n; ++j) {
-      if (i == j) continue;
-      int can = 0;
-      HIP_CHECK(hipDeviceCanAccessPeer(&can, i, j));
-      if (can) {
-        hipError_t e = hipDeviceEnablePeerAccess(j, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
-          (void)hipGetLastError();
-        else
-          (void)hipGetLastError();
-      }
-    }
+    for (int j = 0; j < n; ++j) readable[i][j] = enable_peer_read(i, j);
   }
-  for (int d = 0; d < n; ++d) {
-    for (int s = 0; s < n; ++s) {
-      if (s == d) {
-        double ms = time_kernel_ms(
-            d, [&](hipStream_t st) { launch_copy_f32(src[d], dst[d], count, st); },
-            iters);
-        out[s][d] = (2.0 * count * sizeof(float)) / (ms * 1e6);
-        continue;
-      }
-      int can = 0;
-      HIP_CHECK(hipDeviceCanAccessPeer(&can, d, s));
-      double ms;
-      if (can) {
-        // dst-device kernel pulls from src-device memory over xGMI
-        ms = time_kernel_ms(
-            d, [&](hipStream_t st) { launch_copy_f32(src[s], dst[d], count, st); },
-            iters);
-      } else {
-        ms = time_kernel_ms(
-            d,
-            [&](hipStream_t st) {
-              HIP_CHECK(hipMemcpyPeerAsync(dst[d], d, src[s], s,
-                                           count * sizeof(float), st));
-            },
-            iters);
-      }
-      out[s][d] = (double)(count * sizeof(float)) / (ms * 1e6);
-    }
-  }
-  for (int i = 0; i < n; ++i) {
-    (void)hipSetDevice(i);
-    (void)hipFree(src[i]);
-    (void)hipFree(dst[i]);
-  }
+  for (int d = 0; d < n; ++d)
+    for (int s = 0; s < n; ++s)
+      out[s][d] = time_pair_gbps(s, src[s].ptr, d, dst[d].ptr, count,
+                                 readable[d][s], iters);
   return out;
 }
 
@@ -438,11 +370,83 @@ torch::Tensor resolve_out(const c10::optional<torch::Tensor>& out, int64_t M,
   return C;
 }
 
-void check_gemm_operands(const torch::Tensor& A, const torch::Tensor& B,
-                         const char* bname) {
+// What one GEMM / MFMA binding accepts.
+struct GemmSpec {
+  torch::ScalarType dtype;
+  const char* dtype_msg;
+  bool b_is_nk;            // second operand is Bt [N][K]; otherwise B [K][N]
+  int tile;                // M and N: multiples of it, at least it
+  int k_mult, k_min;
+  const char* extent_msg;  // names tile, k_mult and k_min
+  bool packed_fp4 = false;  // two elements per stored byte; K is an argument
+};
+
+// The validated operands of one call: extents, contiguous A and B, the
+// resolved C, and torch's current stream.
+struct GemmOperands {
+  int M, N, K;
+  torch::Tensor A, B, C;
+  hipStream_t stream;
+  template <typename T>
+  const T* a() const { return static_cast<const T*>(A.data_ptr()); }
+  template <typename T>
+  const T* b() const { return static_cast<const T*>(B.data_ptr()); }
+  float* c() const { return C.data_ptr<float>(); }
+};
+
+// The one operand check of the six GEMM / MFMA bindings, in this order:
+// placement and rank, dtype, inner extent, tile extents, `select(K)` (the
+// binding's variant lookup, may be empty), 16-byte alignment, `out`.
+// packed_k: the K argument of a packed_fp4 binding, not read otherwise.
+GemmOperands gemm_operands(torch::Tensor A, torch::Tensor B,
+                           const c10::optional<torch::Tensor>& out,
+                           const GemmSpec& spec,
+                           const std::function<void(int)>& select = nullptr,
+                           int packed_k = 0) {
+  const char* bname = spec.b_is_nk ? "Bt" : "B";
   TORCH_CHECK(A.is_cuda() && B.is_cuda(), "GPU tensors required");
   TORCH_CHECK(A.device() == B.device(), "operands must share a device");
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2, "A and ", bname, " must be 2-D");
+  TORCH_CHECK(A.scalar_type() == spec.dtype && B.scalar_type() == spec.dtype,
+              spec.dtype_msg);
+  GemmOperands g;
+  g.A = A.contiguous();
+  g.B = B.contiguous();
+  g.M = g.A.size(0);
+  g.N = g.B.size(spec.b_is_nk ? 0 : 1);
+  const int64_t a_cols = g.A.size(1), b_k = g.B.size(spec.b_is_nk ? 1 : 0);
+  if (spec.packed_fp4) {
+    g.K = packed_k;
+    TORCH_CHECK(a_cols * 2 == g.K && b_k * 2 == g.K,
+                "K must equal 2 x packed byte columns");
+  } else {
+    g.K = a_cols;
+    TORCH_CHECK(b_k == g.K, spec.b_is_nk ? "Bt must be [N][K]" : "shape mismatch");
+  }
+  TORCH_CHECK(g.M >= spec.tile && g.N >= spec.tile && g.M % spec.tile == 0 &&
+                  g.N % spec.tile == 0 && g.K % spec.k_mult == 0 &&
+                  g.K >= spec.k_min,
+              spec.extent_msg);
+  if (select) select(g.K);
+  check_aligned16(g.A, "A");
+  check_aligned16(g.B, bname);
+  g.C = resolve_out(out, g.M, g.N, g.A);
+  check_aligned16(g.C, "out");
+  g.stream = at::hip::getCurrentHIPStream().stream();
+  return g;
+}
+
+// One wave per 16x16 tile of C, four waves per block.
+template <typename T>
+torch::Tensor launch_mfma_16x16(void (*kernel)(const T*, const T*, float*, int,
+                                               int, int),
+                                const GemmOperands& g) {
+  constexpr int kWavesPerBlock = 4;  // 256 threads
+  int waves = (g.M / 16) * (g.N / 16);
+  int grid = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWavesPerBlock * 64), 0, g.stream,
+                     g.a<T>(), g.b<T>(), g.c(), g.M, g.N, g.K);
+  return g.C;
 }
 
 void copy_f32(torch::Tensor dst, torch::Tensor src) {
@@ -461,57 +465,20 @@ void copy_f32(torch::Tensor dst, torch::Tensor src) {
 
 torch::Tensor mfma_f32_matmul(torch::Tensor A, torch::Tensor B,
                               c10::optional<torch::Tensor> out) {
-  check_gemm_operands(A, B, "B");
-  TORCH_CHECK(A.scalar_type() == torch::kFloat32 &&
-              B.scalar_type() == torch::kFloat32, "f32 only");
-  A = A.contiguous();
-  B = B.contiguous();
-  int M = A.size(0), K = A.size(1), N = B.size(1);
-  TORCH_CHECK(B.size(0) == K, "shape mismatch");
-  TORCH_CHECK(M >= 16 && N >= 16 && K >= 4 && M % 16 == 0 && N % 16 == 0 &&
-                  K % 4 == 0,
-              "M,N multiples of 16; K multiple of 4, >= 4");
-  check_aligned16(A, "A");
-  check_aligned16(B, "B");
-  auto C = resolve_out(out, M, N, A);
-  check_aligned16(C, "out");
-  int waves = (M / 16) * (N / 16);
-  constexpr int kWavesPerBlock = 4;  // 256 threads
-  int grid = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(mfma_f32_16x16_kernel, dim3(grid),
-                     dim3(kWavesPerBlock * 64), 0, stream.stream(),
-                     A.data_ptr<float>(), B.data_ptr<float>(),
-                     C.data_ptr<float>(), M, N, K);
-  return C;
+  return launch_mfma_16x16<float>(
+      mfma_f32_16x16_kernel,
+      gemm_operands(A, B, out,
+                    {torch::kFloat32, "f32 only", false, 16, 4, 4,
+                     "M,N multiples of 16; K multiple of 4, >= 4"}));
 }
 
 torch::Tensor mfma_bf16_matmul(torch::Tensor A, torch::Tensor B,
                                c10::optional<torch::Tensor> out) {
-  check_gemm_operands(A, B, "B");
-  TORCH_CHECK(A.scalar_type() == torch::kBFloat16 &&
-              B.scalar_type() == torch::kBFloat16, "bf16 only");
-  A = A.contiguous();
-  B = B.contiguous();
-  int M = A.size(0), K = A.size(1), N = B.size(1);
-  TORCH_CHECK(B.size(0) == K, "shape mismatch");
-  TORCH_CHECK(M >= 16 && N >= 16 && K >= 32 && M % 16 == 0 && N % 16 == 0 &&
-                  K % 32 == 0,
-              "M,N multiples of 16; K multiple of 32, >= 32");
-  check_aligned16(A, "A");
-  check_aligned16(B, "B");
-  auto C = resolve_out(out, M, N, A);
-  check_aligned16(C, "out");
-  int waves = (M / 16) * (N / 16);
-  constexpr int kWavesPerBlock = 4;
-  int grid = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(mfma_bf16_16x16_kernel, dim3(grid),
-                     dim3(kWavesPerBlock * 64), 0, stream.stream(),
-                     reinterpret_cast<const __hip_bfloat16*>(A.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(B.data_ptr()),
-                     C.data_ptr<float>(), M, N, K);
-  return C;
+  return launch_mfma_16x16<__hip_bfloat16>(
+      mfma_bf16_16x16_kernel,
+      gemm_operands(A, B, out,
+                    {torch::kBFloat16, "bf16 only", false, 16, 32, 32,
+                     "M,N multiples of 16; K multiple of 32, >= 32"}));
 }
 
 // BK of the 128^2 kernel: 32 or 64; 0 picks the widest K-step that divides K
@@ -539,29 +506,18 @@ void launch_bf16_tile(int bk, int swizzle, dim3 grid, hipStream_t s,
 
 torch::Tensor gemm_bf16_bt(torch::Tensor A, torch::Tensor Bt, int swizzle,
                            int bk, c10::optional<torch::Tensor> out) {
-  check_gemm_operands(A, Bt, "Bt");
-  TORCH_CHECK(A.scalar_type() == torch::kBFloat16 &&
-              Bt.scalar_type() == torch::kBFloat16, "bf16 only");
-  A = A.contiguous();
-  Bt = Bt.contiguous();
-  int M = A.size(0), K = A.size(1), N = Bt.size(0);
-  TORCH_CHECK(Bt.size(1) == K, "Bt must be [N][K]");
-  TORCH_CHECK(M >= 128 && N >= 128 && K >= 32 && M % 128 == 0 &&
-                  N % 128 == 0 && K % 32 == 0,
-              "M,N multiples of 128; K multiple of 32, >= 32");
-  TORCH_CHECK(swizzle == 0 || swizzle == 1, "swizzle must be 0 or 1");
-  bk = resolve_bf16_bk(bk, K);
-  check_aligned16(A, "A");
-  check_aligned16(Bt, "Bt");
-  auto C = resolve_out(out, M, N, A);
-  check_aligned16(C, "out");
-  int grid = (M / 128) * (N / 128);
-  auto stream = at::hip::getCurrentHIPStream();
-  launch_bf16_tile(bk, swizzle, dim3(grid), stream.stream(),
-                   reinterpret_cast<const __hip_bfloat16*>(A.data_ptr()),
-                   reinterpret_cast<const __hip_bfloat16*>(Bt.data_ptr()),
-                   C.data_ptr<float>(), M, N, K);
-  return C;
+  auto g = gemm_operands(
+      A, Bt, out,
+      {torch::kBFloat16, "bf16 only", true, 128, 32, 32,
+       "M,N multiples of 128; K multiple of 32, >= 32"},
+      [&](int K) {
+        TORCH_CHECK(swizzle == 0 || swizzle == 1, "swizzle must be 0 or 1");
+        bk = resolve_bf16_bk(bk, K);
+      });
+  launch_bf16_tile(bk, swizzle, dim3((g.M / 128) * (g.N / 128)), g.stream,
+                   g.a<__hip_bfloat16>(), g.b<__hip_bfloat16>(), g.c(), g.M, g.N,
+                   g.K);
+  return g.C;
 }
 
 // Enqueues one size^3 GEMM on a stream: (stream, A, Bt, C).
@@ -587,7 +543,7 @@ template <typename T>
 std::vector<std::vector<double>> time_gemm_tflops(
     int device, int size, int iters, int rounds, size_t operand_elems,
     void (*fill)(T*, size_t, unsigned), const std::vector<GemmLaunch<T>>& launches) {
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope(device);
   mfma_warmup(device, 20000);
   DeviceBuf<T> A(device, operand_elems), Bt(device, operand_elems);
   DeviceBuf<float> C(device, (size_t)size * size);
@@ -717,29 +673,28 @@ std::vector<std::vector<double>> time_256_tflops(
                              launches);
 }
 
+// The tensor binding of one 256^2 format: operands checked against `spec`,
+// `code` looked up in `table`, one launch on the current stream.
+template <typename T, size_t NV>
+torch::Tensor gemm_256_bt(torch::Tensor A, torch::Tensor Bt,
+                          const c10::optional<torch::Tensor>& out,
+                          const GemmSpec& spec,
+                          const Gemm256Variant<T> (&table)[NV], int code,
+                          const char* what, int packed_k = 0) {
+  Gemm256Kernel<T> kernel = nullptr;
+  const GemmOperands g = gemm_operands(
+      A, Bt, out, spec, [&](int) { kernel = find_variant(table, code, what); },
+      packed_k);
+  launch_256(kernel, g.stream, g.a<T>(), g.b<T>(), g.c(), g.M, g.N, g.K);
+  return g.C;
+}
+
 torch::Tensor gemm_bf16_8ph_bt(torch::Tensor A, torch::Tensor Bt, int variant,
                                c10::optional<torch::Tensor> out) {
-  check_gemm_operands(A, Bt, "Bt");
-  TORCH_CHECK(A.scalar_type() == torch::kBFloat16 &&
-              Bt.scalar_type() == torch::kBFloat16, "bf16 only");
-  A = A.contiguous();
-  Bt = Bt.contiguous();
-  int M = A.size(0), K = A.size(1), N = Bt.size(0);
-  TORCH_CHECK(Bt.size(1) == K, "Bt must be [N][K]");
-  TORCH_CHECK(M >= 256 && N >= 256 && M % 256 == 0 && N % 256 == 0 &&
-                  K % 64 == 0 && K >= 192,
-              "M,N multiples of 256; K multiple of 64, >= 192");
-  auto kernel = find_variant(kBf16Variants8ph, variant, "8-phase variant");
-  check_aligned16(A, "A");
-  check_aligned16(Bt, "Bt");
-  auto C = resolve_out(out, M, N, A);
-  check_aligned16(C, "out");
-  auto stream = at::hip::getCurrentHIPStream();
-  launch_256(kernel, stream.stream(),
-             reinterpret_cast<const __hip_bfloat16*>(A.data_ptr()),
-             reinterpret_cast<const __hip_bfloat16*>(Bt.data_ptr()),
-             C.data_ptr<float>(), M, N, K);
-  return C;
+  return gemm_256_bt(A, Bt, out,
+                     {torch::kBFloat16, "bf16 only", true, 256, 64, 192,
+                      "M,N multiples of 256; K multiple of 64, >= 192"},
+                     kBf16Variants8ph, variant, "8-phase variant");
 }
 
 double gemm_bf16_8ph_tflops(int device, int size, int iters, int variant) {
@@ -773,55 +728,21 @@ py::dict gemm_bf16_8ph_ab(int device, int size, int iters, int rounds,
 
 torch::Tensor gemm_fp8_mx_bt(torch::Tensor A, torch::Tensor Bt, int shape,
                              c10::optional<torch::Tensor> out) {
-  check_gemm_operands(A, Bt, "Bt");
-  TORCH_CHECK(A.scalar_type() == torch::kUInt8 &&
-              Bt.scalar_type() == torch::kUInt8,
-              "raw e4m3 bytes expected (uint8 view of float8_e4m3fn)");
-  A = A.contiguous();
-  Bt = Bt.contiguous();
-  int M = A.size(0), K = A.size(1), N = Bt.size(0);
-  TORCH_CHECK(Bt.size(1) == K, "Bt must be [N][K]");
-  TORCH_CHECK(M >= 256 && N >= 256 && M % 256 == 0 && N % 256 == 0 &&
-                  K % 128 == 0 && K >= 256,
-              "M,N multiples of 256; K multiple of 128, >= 256");
-  auto kernel = find_variant(kFp8MxShapes, shape, "fp8 MX shape code");
-  check_aligned16(A, "A");
-  check_aligned16(Bt, "Bt");
-  auto C = resolve_out(out, M, N, A);
-  check_aligned16(C, "out");
-  auto stream = at::hip::getCurrentHIPStream();
-  launch_256(kernel, stream.stream(),
-             reinterpret_cast<const unsigned char*>(A.data_ptr()),
-             reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-             C.data_ptr<float>(), M, N, K);
-  return C;
+  return gemm_256_bt(
+      A, Bt, out,
+      {torch::kUInt8, "raw e4m3 bytes expected (uint8 view of float8_e4m3fn)",
+       true, 256, 128, 256, "M,N multiples of 256; K multiple of 128, >= 256"},
+      kFp8MxShapes, shape, "fp8 MX shape code");
 }
 
 torch::Tensor gemm_fp4_mx_bt(torch::Tensor A, torch::Tensor Bt, int K, int shape,
                              c10::optional<torch::Tensor> out) {
   // A [M][K/2], Bt [N][K/2]: e2m1 nibble-packed (low nibble = even k)
-  check_gemm_operands(A, Bt, "Bt");
-  TORCH_CHECK(A.scalar_type() == torch::kUInt8 &&
-              Bt.scalar_type() == torch::kUInt8, "packed e2m1 bytes expected");
-  A = A.contiguous();
-  Bt = Bt.contiguous();
-  int M = A.size(0), N = Bt.size(0);
-  TORCH_CHECK((long)A.size(1) * 2 == K && (long)Bt.size(1) * 2 == K,
-              "K must equal 2 x packed byte columns");
-  TORCH_CHECK(M >= 256 && N >= 256 && M % 256 == 0 && N % 256 == 0 &&
-                  K % 256 == 0 && K >= 512,
-              "M,N multiples of 256; K multiple of 256, >= 512");
-  auto kernel = find_variant(kFp4MxShapes, shape, "fp4 MX shape code");
-  check_aligned16(A, "A");
-  check_aligned16(Bt, "Bt");
-  auto C = resolve_out(out, M, N, A);
-  check_aligned16(C, "out");
-  auto stream = at::hip::getCurrentHIPStream();
-  launch_256(kernel, stream.stream(),
-             reinterpret_cast<const unsigned char*>(A.data_ptr()),
-             reinterpret_cast<const unsigned char*>(Bt.data_ptr()),
-             C.data_ptr<float>(), M, N, K);
-  return C;
+  return gemm_256_bt(
+      A, Bt, out,
+      {torch::kUInt8, "packed e2m1 bytes expected", true, 256, 256, 512,
+       "M,N multiples of 256; K multiple of 256, >= 512", true},
+      kFp4MxShapes, shape, "fp4 MX shape code", K);
 }
 
 double gemm_fp8_mx_tflops(int device, int size, int iters, int shape) {
@@ -886,7 +807,7 @@ py::dict device_info(int device) {
   d["pciDomainID"] = prop.pciDomainID;
   d["pciDeviceID"] = prop.pciDeviceID;
   size_t free_b = 0, total_b = 0;
-  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope(device);
   HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
   d["freeMem"] = (long long)free_b;
   return d;

@@ -267,20 +267,16 @@ def validate_gpus(
         if i < 0 or i >= n:
             continue
         hbm = ext.stream_bandwidth_gbps(i, 1024, 5)
-        # prefer the 8-phase 256^2 pipelined structure (~1000 TF) when the
-        # shape allows; fall back to the 128^2 double-buffered kernel
-        if size % 256 == 0 and size >= 192:
-            tflops = ext.gemm_bf16_8ph_tflops(i, size, iters)
-        else:
-            tflops = ext.gemm_bf16_tflops(i, size, iters)
+        # the 8-phase 256^2 pipelined structure (~1000 TF); size always fits it
+        tflops = ext.gemm_bf16_8ph_tflops(i, size, iters)
         entry = {
             "index": i,
             "hbm_gbps": round(hbm, 1),
             "bf16_tflops": round(tflops, 1),
         }
-        if fp8 and size % 256 == 0 and size >= 256:
+        if fp8:
             entry["fp8_tflops"] = round(ext.gemm_fp8_mx_tflops(i, size, iters), 1)
-        if fp8 and size % 256 == 0 and size >= 512:
+        if fp8 and size >= 512:  # the fp4 kernel needs K >= 512
             entry["fp4_tflops"] = round(ext.gemm_fp4_mx_tflops(i, size, iters), 1)
         if memtest_mib > 0:
             entry["memtest"] = memtest_gpu(i, memtest_mib)

@@ -141,6 +141,27 @@ def test_hbm_stream_bandwidth_floor(ext):
     assert bw > 3800, f"HBM copy bandwidth regressed: {bw} GB/s (floor 3800 = 75% of measured 5092)"
 
 
+def test_probes_leave_the_callers_device_current(ext):
+    """Every probe that works on another GPU hands the thread back on the
+    device it came in on: torch allocates on whatever HIP calls current."""
+    import torch
+
+    if ext.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    home = torch.empty(1, device="cuda").device.index
+    calls = {
+        "mfma_warmup": lambda: ext.mfma_warmup(1, 100),
+        "stream_bandwidth_gbps": lambda: ext.stream_bandwidth_gbps(1, 16, 1),
+        "gemm_bf16_8ph_tflops": lambda: ext.gemm_bf16_8ph_tflops(1, 256, 1),
+        "device_info": lambda: ext.device_info(1),
+        "p2p_matrix": lambda: ext.p2p_matrix(4, 1),
+    }
+    for name, call in calls.items():
+        call()
+        after = torch.empty(1, device="cuda").device.index
+        assert after == home, f"{name} left device {after} current, not {home}"
+
+
 def test_probe_output_shape():
     require_gpu()
     from gpu_docker_api_amd.ops import hipcore

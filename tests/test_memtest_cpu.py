@@ -124,9 +124,6 @@ class StubExt:
     def gemm_bf16_8ph_tflops(self, i, size, iters):
         return 1000.0
 
-    def gemm_bf16_tflops(self, i, size, iters):
-        return 800.0
-
     def gemm_fp8_mx_tflops(self, i, size, iters):
         return 1900.0
 
