@@ -12,6 +12,9 @@
 //   * Per-CU MFMA and LDS check (cu_check.hip): exact tiles in bf16, MX-fp8
 //     and MX-fp4 checked on the CU that computed them, its whole LDS
 //     pattern-tested, every result tagged with the XCC and CU id.
+//   * Checked GEMM loop (gemm_check.hip): the 256^2 kernels at full size on
+//     exactly-summable operands, every result verified on the device with
+//     integer row and column checksums per tile.
 //   * MFMA warm-up / validation tiles: the exact-f32 16x16x4 MFMA (operand
 //     maps documented in the CDNA4 guide) and the bf16 16x16x32 MFMA —
 //     clock ramp before measuring, numerics check against torch fp32.
@@ -815,6 +818,8 @@ py::dict device_info(int device) {
 
 }  // namespace
 
+#include "gemm_check.hip"
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X native core: bandwidth probes + MFMA tiles";
   m.def("probe_fill", &probe_fill, py::arg("kind"), py::arg("n"), py::arg("seed"));
@@ -882,4 +887,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cu_check_tile", &cu_check::cu_check_tile, py::arg("fmt"),
         py::arg("tile"), py::arg("seed"));
   m.def("cu_check_geometry", &cu_check::cu_check_geometry);
+  m.def("gemm_check", &gemm_check::gemm_check, py::arg("device"), py::arg("kind"),
+        py::arg("size"), py::arg("iters"), py::arg("seed"), py::arg("range"),
+        py::arg("code") = -1, py::arg("max_records") = 32,
+        py::arg("inject") = std::vector<std::vector<long long>>{},
+        py::arg("loop") = gemm_check::kLoopNames[gemm_check::kDefaultLoop]);
+  m.def("gemm_check_fill", &gemm_check::gemm_check_fill, py::arg("kind"),
+        py::arg("operand"), py::arg("rows"), py::arg("K"), py::arg("seed"),
+        py::arg("range"));
+  m.def("gemm_check_expected", &gemm_check::gemm_check_expected, py::arg("kind"),
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("seed"), py::arg("range"));
+  m.def("gemm_check_verify", &gemm_check::gemm_check_verify, py::arg("kind"),
+        py::arg("C"), py::arg("K"), py::arg("seed"), py::arg("range"),
+        py::arg("max_records") = 32);
+  m.def("gemm_check_geometry", &gemm_check::gemm_check_geometry);
 }

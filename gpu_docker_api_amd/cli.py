@@ -254,14 +254,22 @@ def res_validate(
     cu_check: int = typer.Option(
         0, "--cu-check", help="also check every CU's MFMA and LDS for this many rounds (0 = off)"
     ),
+    gemm_check: int = typer.Option(
+        0,
+        "--gemm-check",
+        help="also run this many checksum-verified full-size GEMMs per format (0 = off)",
+    ),
 ):
     """Burn-in free GPUs (HBM bandwidth + bf16/MX-fp8/MX-fp4 MFMA TFLOPS,
-    optionally an HBM pattern memory test and a per-CU compute check)."""
+    optionally an HBM pattern memory test, a per-CU compute check and a
+    checked GEMM loop)."""
     body = {"size": size, "iters": iters}
     if memtest_mib:
         body["memtestMiB"] = memtest_mib
     if cu_check > 0:
         body["cuCheck"] = cu_check
+    if gemm_check != 0:
+        body["gemmCheck"] = gemm_check
     with _client() as c:
         _show(
             c.post(

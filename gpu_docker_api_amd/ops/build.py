@@ -46,6 +46,7 @@ def build_hipcore(force: bool = False) -> str:
         os.path.join(CSRC, "gemm_fp8_mx.hip"),
         os.path.join(CSRC, "hbm_memtest.hip"),
         os.path.join(CSRC, "cu_check.hip"),
+        os.path.join(CSRC, "gemm_check.hip"),
     ]
     out = os.path.join(OPS, "_hipcore.so")
     if not force and _newer(out, src, *[p for p in includes if os.path.exists(p)]):

@@ -240,6 +240,172 @@ def cu_check_gpu(
     return report
 
 
+GEMM_CHECK_SEED = 0x6E44C4EC5EED0001
+GEMM_CHECK_KINDS = ("bf16", "fp8", "fp4")
+GEMM_CHECK_TILE = 256
+GEMM_CHECK_MIN_SIZE = {"bf16": 256, "fp8": 256, "fp4": 512}
+GEMM_CHECK_CODE = {"bf16": 0, "fp8": 16, "fp4": 16}  # the kernels validate_gpus times
+GEMM_CHECK_RECORDS = 64
+_NXCD = 8  # gemm_8ph::NXCD
+
+
+def gemm_check_range(kind: str, K: int) -> int:
+    """The operand range of the checked GEMM loop at inner extent K, the
+    largest for which every partial sum stays an integer below 2^24 product
+    granules (csrc/gemm_check.hip): bf16 numerators m/16 in [-r, r] with
+    r = min(127, floor(sqrt(2^24 / K))); e4m3 exponent fields 6..6+w-1 with w
+    the largest of 1..4 with (15 * 2^(w-1))^2 * K <= 2^24; e2m1 all 16 codes."""
+    import math
+
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be positive")
+    if kind == "bf16":
+        r = min(127, math.isqrt((1 << 24) // K))
+        if r < 1:
+            raise ValueError(f"no exact bf16 operand range at K = {K}")
+        return r
+    if kind == "fp8":
+        for w in (4, 3, 2, 1):
+            if (15 << (w - 1)) ** 2 * K <= 1 << 24:
+                return w
+        raise ValueError(f"no exact fp8 operand range at K = {K}")
+    if kind == "fp4":
+        if 144 * K > 1 << 24:
+            raise ValueError(f"no exact fp4 operand range at K = {K}")
+        return 16
+    raise ValueError(f"unknown kind {kind!r} (bf16, fp8, fp4)")
+
+
+def _xcd_start(x: int, nwg: int) -> int:
+    q, r = divmod(nwg, _NXCD)
+    return x * (q + 1) if x < r else r * (q + 1) + (x - r) * q
+
+
+def gemm_check_owner(tile_row: int, tile_col: int, tiles_n: int, nwg: int, xcd_remap: bool):
+    """(blockIdx.x, blockIdx.x % 8) of the workgroup of an `nwg`-workgroup
+    256^2 GEMM launch that computes tile (tile_row, tile_col): the inverse of
+    tile_coord in csrc/gemm_8phase_common.h. With xcd_remap (the odd bf16
+    codes) workgroup b takes tile start(b % 8) + b // 8, where XCD x owns a
+    contiguous range of tiles; the second value is the XCD a workgroup runs
+    on under round-robin dispatch."""
+    t = tile_row * tiles_n + tile_col
+    if not (0 <= tile_col < tiles_n and 0 <= t < nwg):
+        raise ValueError(f"tile ({tile_row}, {tile_col}) is outside the launch")
+    bid = t
+    if xcd_remap:
+        q, r = divmod(nwg, _NXCD)
+        # the first r XCDs own q + 1 tiles each, the others q
+        xcd = t // (q + 1) if t < r * (q + 1) else r + (t - r * (q + 1)) // q
+        bid = (t - _xcd_start(xcd, nwg)) * _NXCD + xcd
+    return bid, bid % _NXCD
+
+
+def gemm_check_fold(raw: dict, tiles_n: int, nwg: int, xcd_remap: bool) -> dict:
+    """Group the records of a checked GEMM run by (iteration, tile). Pure
+    Python. Each bad tile names the workgroup that computed it and lists its
+    mismatching rows and columns in product granules; `element` appears only
+    where it can be pinned: exactly one row and one column of the tile
+    mismatch, by the same delta, and nothing in it is malformed. A whole line
+    of bad tiles (what a flipped operand word gives) is listed in `bands`.
+    Records are capped on the device, counts are not: `records_truncated`
+    says that findings exist beyond the ones folded here."""
+    tiles: dict = {}
+    for rec in raw["records"]:
+        key = (int(rec["iter"]), int(rec["tile_row"]), int(rec["tile_col"]))
+        t = tiles.setdefault(key, {"rows": [], "cols": [], "malformed": []})
+        if rec["type"] == "malformed":
+            t["malformed"].append(
+                {"row": int(rec["row"]), "col": int(rec["col"]), "bits": int(rec["bits"])}
+            )
+        else:
+            name = "row" if rec["type"] == "row" else "col"
+            t[name + "s"].append(
+                {name: int(rec["index"]), "got": int(rec["got"]), "want": int(rec["want"])}
+            )
+    tiles_m = max(1, nwg // tiles_n)
+    bad_tiles = []
+    by_mod8 = [0] * _NXCD
+    lines: dict = {}
+    for key in sorted(tiles):
+        it, tr, tc = key
+        t = tiles[key]
+        block, mod8 = gemm_check_owner(tr, tc, tiles_n, nwg, xcd_remap)
+        entry = {
+            "iter": it,
+            "tile": [tr, tc],
+            "block": block,
+            "block_mod8": mod8,
+            "rows": sorted(t["rows"], key=lambda e: e["row"]),
+            "cols": sorted(t["cols"], key=lambda e: e["col"]),
+            "malformed": sorted(t["malformed"], key=lambda e: (e["row"], e["col"])),
+        }
+        if len(t["rows"]) == 1 and len(t["cols"]) == 1 and not t["malformed"]:
+            dr = t["rows"][0]["got"] - t["rows"][0]["want"]
+            dc = t["cols"][0]["got"] - t["cols"][0]["want"]
+            if dr == dc:
+                entry["element"] = {
+                    "row": tr * GEMM_CHECK_TILE + t["rows"][0]["row"],
+                    "col": tc * GEMM_CHECK_TILE + t["cols"][0]["col"],
+                    "delta": dr,
+                }
+        bad_tiles.append(entry)
+        by_mod8[mod8] += 1
+        lines.setdefault((it, "row", tr), set()).add(tc)
+        lines.setdefault((it, "col", tc), set()).add(tr)
+    bands = [
+        {"iter": it, "axis": axis, "index": index, "tiles": len(members)}
+        for (it, axis, index), members in sorted(lines.items())
+        if len(members) > 1 and len(members) == (tiles_n if axis == "row" else tiles_m)
+    ]
+    errors = {k: int(raw["errors"][k]) for k in ("rows", "cols", "malformed")}
+    return {
+        "errors": errors,
+        "bad_tiles": bad_tiles,
+        "bands": bands,
+        "by_block_mod8": by_mod8,
+        "records_truncated": sum(errors.values()) > len(raw["records"]),
+    }
+
+
+def gemm_check_gpu(
+    index: int,
+    size: int = 4096,
+    iters: int = 10,
+    formats=GEMM_CHECK_KINDS,
+    seed: int = GEMM_CHECK_SEED,
+    inject: Optional[list] = None,
+) -> dict:
+    """Checked GEMM loop on GPU `index` (csrc/gemm_check.hip): per format,
+    `iters` full-size launches of the kernel validate_gpus times, on operands
+    whose sums are exact, each result verified on the device with integer row
+    and column checksums per 256^2 tile. fp4 is skipped below size 512, as in
+    the throughput tier. `tflops` is information, not a health criterion: the
+    exact operand sets toggle fewer bits than the probes' hash fills."""
+    ext = load_ext()
+    size = max(GEMM_CHECK_TILE, (int(size) // GEMM_CHECK_TILE) * GEMM_CHECK_TILE)
+    tiles = size // GEMM_CHECK_TILE
+    report = {"size": size, "iters": int(iters), "formats": {}}
+    total = 0
+    for kind in formats:
+        if size < GEMM_CHECK_MIN_SIZE[kind]:
+            continue
+        code = GEMM_CHECK_CODE[kind]
+        raw = ext.gemm_check(
+            index, kind, size, int(iters), seed, gemm_check_range(kind, size), code,
+            GEMM_CHECK_RECORDS, list(inject or []),
+        )
+        entry = gemm_check_fold(raw, tiles, tiles * tiles, kind == "bf16" and code % 2 == 1)
+        entry["operand_errors"] = int(raw["operand_errors"])
+        entry["seconds"] = round(raw["seconds"], 4)
+        entry["tflops"] = round(raw["tflops"], 1)
+        entry["checked_bytes"] = int(raw["checked_bytes"])
+        total += sum(entry["errors"].values()) + entry["operand_errors"]
+        report["formats"][kind] = entry
+    report["errors_total"] = total
+    return report
+
+
 def validate_gpus(
     indices: Optional[list] = None,
     size: int = 4096,
@@ -247,6 +413,7 @@ def validate_gpus(
     fp8: bool = True,
     memtest_mib: int = 0,
     cu_rounds: int = 0,
+    gemm_check_iters: int = 0,
 ) -> dict:
     """Per-GPU health burn-in: HBM stream bandwidth + dense bf16 MFMA GEMM
     (the 8-phase 256^2 structure, ~1.1 PF) + the MX-fp8 path (block-scaled
@@ -257,7 +424,10 @@ def validate_gpus(
     (memtest_gpu) and is unhealthy if a single word read back wrong. With
     cu_rounds > 0 each GPU also gets the per-CU MFMA and LDS check
     (cu_check_gpu) and is unhealthy if a single result or LDS word was wrong;
-    CUs the pass did not reach are reported, not judged."""
+    CUs the pass did not reach are reported, not judged. With
+    gemm_check_iters > 0 each GPU also gets the checked GEMM loop
+    (gemm_check_gpu) at `size` and is unhealthy if a single checksum, element
+    or stored operand was wrong in any format."""
     ext = load_ext()
     n = ext.device_count()
     idx = list(indices) if indices else list(range(n))
@@ -282,6 +452,8 @@ def validate_gpus(
             entry["memtest"] = memtest_gpu(i, memtest_mib)
         if cu_rounds > 0:
             entry["cu_check"] = cu_check_gpu(i, cu_rounds)
+        if gemm_check_iters > 0:
+            entry["gemm_check"] = gemm_check_gpu(i, size, gemm_check_iters)
         report["gpus"].append(entry)
     vals = [g["bf16_tflops"] for g in report["gpus"]]
     if vals:
@@ -292,6 +464,8 @@ def validate_gpus(
                 g["healthy"] = bool(g["healthy"] and g["memtest"]["errors"] == 0)
             if "cu_check" in g:
                 g["healthy"] = bool(g["healthy"] and g["cu_check"]["errors"]["total"] == 0)
+            if "gemm_check" in g:
+                g["healthy"] = bool(g["healthy"] and g["gemm_check"]["errors_total"] == 0)
     return report
 
 
@@ -301,11 +475,17 @@ async def validate_gpus_async(
     iters: int = 5,
     memtest_mib: int = 0,
     cu_rounds: int = 0,
+    gemm_check_iters: int = 0,
 ) -> dict:
     return await asyncio.get_running_loop().run_in_executor(
         None,
         lambda: validate_gpus(
-            indices, size, iters, memtest_mib=memtest_mib, cu_rounds=cu_rounds
+            indices,
+            size,
+            iters,
+            memtest_mib=memtest_mib,
+            cu_rounds=cu_rounds,
+            gemm_check_iters=gemm_check_iters,
         ),
     )
 

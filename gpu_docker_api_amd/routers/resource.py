@@ -26,7 +26,8 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
     async def gpus_validate(request: Request):
         """MI355X extension: burn-in the node's FREE GPUs (HBM bandwidth +
         dense bf16 MFMA GEMM, with `memtestMiB` an HBM pattern memory test
-        and with `cuCheck` a per-CU MFMA and LDS check) before trusting them
+        with `cuCheck` a per-CU MFMA and LDS check, with `gemmCheck` a
+        checked loop of the full-size GEMMs) before trusting them
         with placements. Busy GPUs are skipped unless explicitly listed."""
         try:
             body = await request.json()
@@ -58,6 +59,9 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
             cu_rounds = body.get("cuCheck", 0)
             if isinstance(cu_rounds, bool) or not isinstance(cu_rounds, int):
                 raise TypeError("cuCheck must be an int")
+            gemm_check = body.get("gemmCheck", 0)
+            if isinstance(gemm_check, bool) or not isinstance(gemm_check, int):
+                raise TypeError("gemmCheck must be an int")
         except (TypeError, ValueError):
             from .codes import Code
             from .response import error
@@ -73,6 +77,9 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
             extra = {}
             if cu_rounds != 0:
                 extra["cu_rounds"] = max(1, min(cu_rounds, 4096))
+            # checked GEMM loop: off at 0, else 1 .. 100000 iterations a format
+            if gemm_check != 0:
+                extra["gemm_check_iters"] = max(1, min(gemm_check, 100000))
             report = await hipcore.validate_gpus_async(
                 idx,
                 max(256, min(size, 16384)),
