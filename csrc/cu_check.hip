@@ -53,10 +53,12 @@
 // itself whatever it finds.
 //
 // Detector self-test: inject entries {workgroup, test, tile_or_round,
-// lane_or_word, xor_mask} flip bits of the named lane's first accumulator
-// (after the chain, before the compare) or of the named LDS word (between
-// fill and first verify). They change values only, never an address; the
-// host rejects entries out of range and the kernel bounds the LDS word again.
+// lane_or_word, xor_mask, sub} flip bits of accumulator register sub (0..3)
+// of the named lane (after the chain, before the compare) or of the named
+// LDS word, in phase sub: 0 between fill and first verify, 1 between the
+// first verify's complement store and the second verify. sub may be left
+// out and is then 0. Entries change values only, never an address; the host
+// rejects entries out of range and the kernel bounds the LDS word again.
 //
 // Included by hipcore.hip (needs the torch headers, hip_host.h for HIP_CHECK
 // and the resource owners the driver holds, and hbm_memtest.hip's fmix32).
@@ -87,7 +89,8 @@ constexpr int kRecValid = 0, kRecXcc = 1, kRecHwId = 2, kRecCounts = 3,
 constexpr int kRecWords = kWaves * kRecWaveWords;
 constexpr u32 kRecMagic = 0xC0C4EC01u;
 
-constexpr int kInjectWords = 5;
+constexpr int kInjectWords = 6;
+constexpr int kLdsPhases = 2;
 constexpr int kMaxInject = 64;
 constexpr int kMaxRounds = 65536;
 constexpr int kMaxGridMult = 8;
@@ -253,8 +256,12 @@ __device__ __forceinline__ void check_tile(
   for (int i = 0; i < n_inject; ++i) {
     const u32* e = inject + kInjectWords * i;
     if (e[0] == blockIdx.x && e[1] == (u32)FMT && e[2] == t && e[3] == (u32)lane) {
-      const float a0 = acc[0];
-      acc[0] = __uint_as_float(__float_as_uint(a0) ^ e[4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        // through a scalar, as in the compare below
+        const float a = acc[r];
+        if (e[5] == (u32)r) acc[r] = __uint_as_float(__float_as_uint(a) ^ e[4]);
+      }
     }
   }
   const f32x4 want = expect_tile<FMT>(base, lane);
@@ -293,6 +300,25 @@ __device__ __forceinline__ void lds_verify(
   }
 }
 
+// Apply the LDS inject entries of this workgroup, round and phase. n_inject
+// is uniform over the grid, so every thread takes the barrier or none does.
+__device__ __forceinline__ void lds_inject(u32x4* lds, u32 lds_vecs, u32 tid,
+                                           u32 round, u32 phase,
+                                           const u32* __restrict__ inject,
+                                           int n_inject) {
+  if (n_inject > 0) {
+    if (tid == 0) {
+      for (int i = 0; i < n_inject; ++i) {
+        const u32* e = inject + kInjectWords * i;
+        if (e[0] == blockIdx.x && e[1] == (u32)kLds && e[2] == round &&
+            e[3] < 4 * lds_vecs && e[5] == phase)
+          reinterpret_cast<u32*>(lds)[e[3]] ^= e[4];
+      }
+    }
+    __syncthreads();
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void cu_check_kernel(
     u32* __restrict__ out, int rounds, u32 seed_lo, u32 seed_hi, u32 lds_vecs,
     const u32* __restrict__ inject, int n_inject) {
@@ -316,21 +342,12 @@ __global__ __launch_bounds__(kThreads) void cu_check_kernel(
     const u32 salt = seed_lo + round;
     for (u32 v = tid; v < lds_vecs; v += kThreads) lds[v] = lds_pattern(v, salt);
     __syncthreads();
-    if (n_inject > 0) {  // uniform over the grid: every thread takes the barrier
-      if (tid == 0) {
-        for (int i = 0; i < n_inject; ++i) {
-          const u32* e = inject + kInjectWords * i;
-          if (e[0] == blockIdx.x && e[1] == (u32)kLds && e[2] == round &&
-              e[3] < 4 * lds_vecs)
-            reinterpret_cast<u32*>(lds)[e[3]] ^= e[4];
-        }
-      }
-      __syncthreads();
-    }
+    lds_inject(lds, lds_vecs, tid, round, 0, inject, n_inject);
     // another wave AND another lane than the writer, twice
     lds_verify<true>(lds, lds_vecs, (tid + 65) & (kThreads - 1), salt, 0u, st,
                      round * 8 + 3, round, lane);
     __syncthreads();
+    lds_inject(lds, lds_vecs, tid, round, 1, inject, n_inject);
     lds_verify<false>(lds, lds_vecs, (tid + 130) & (kThreads - 1), salt, ~0u, st,
                       round * 8 + 4, round, lane);
     __syncthreads();
@@ -435,6 +452,8 @@ py::dict cu_check_geometry() {
   d["max_grid_mult"] = kMaxGridMult;
   d["max_launches"] = kMaxLaunches;
   d["max_inject"] = kMaxInject;
+  d["inject_words"] = kInjectWords;
+  d["lds_phases"] = kLdsPhases;
   return d;
 }
 
@@ -443,7 +462,7 @@ py::dict cu_check_geometry() {
 // ---------------------------------------------------------------------------
 
 struct Inject {
-  u32 workgroup, test, index, lane_or_word, mask;
+  u32 workgroup, test, index, lane_or_word, mask, sub;
 };
 
 struct DriverResult {
@@ -495,7 +514,7 @@ DriverResult run_driver(int device, int rounds, u64 seed, int grid_mult,
   std::vector<u32> inj_host;
   for (auto& in : inject) {
     const u32 e[kInjectWords] = {in.workgroup, in.test, in.index,
-                                 in.lane_or_word, in.mask};
+                                 in.lane_or_word, in.mask, in.sub};
     inj_host.insert(inj_host.end(), e, e + kInjectWords);
   }
   DeviceBuf<u32> inj(device, std::max<size_t>(inj_host.size(), 4));
@@ -555,14 +574,21 @@ py::dict cu_check(int device, int rounds, u64 seed, int grid_mult,
               " inject entries");
   std::vector<Inject> inj;
   for (auto& e : inject) {
-    TORCH_CHECK(e.size() == kInjectWords,
+    TORCH_CHECK(e.size() == kInjectWords - 1 || e.size() == kInjectWords,
                 "inject: entries are (workgroup, test, tile_or_round, "
-                "lane_or_word, xor_mask)");
+                "lane_or_word, xor_mask[, sub])");
     for (long long x : e)
       TORCH_CHECK(x >= 0 && x <= 0xFFFFFFFFll, "inject: ", x,
                   " is not an unsigned 32-bit value");
     TORCH_CHECK(e[1] < kNumTests, "inject: test ", e[1], " is not one of 0..3");
-    inj.push_back({(u32)e[0], (u32)e[1], (u32)e[2], (u32)e[3], (u32)e[4]});
+    const long long sub = e.size() == kInjectWords ? e[5] : 0;
+    if (e[1] == kLds) {
+      TORCH_CHECK(sub < kLdsPhases, "inject: phase ", sub, " is not 0 or 1");
+    } else {
+      TORCH_CHECK(sub < 4, "inject: register ", sub, " is not one of 0..3");
+    }
+    inj.push_back({(u32)e[0], (u32)e[1], (u32)e[2], (u32)e[3], (u32)e[4],
+                   (u32)sub});
   }
   DriverResult r;
   {

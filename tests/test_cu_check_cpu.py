@@ -65,6 +65,70 @@ def test_fmix32_known_values():
     assert int(cr.fmix32(np.uint64(1))) == 0x514E28B7
 
 
+def test_lane_reg_map_is_a_bijection_onto_the_tile():
+    cells = {cr.lane_reg_to_row_col(lane, reg) for lane in range(64) for reg in range(4)}
+    assert cells == {(row, col) for row in range(16) for col in range(16)}
+    # the corners of the layout, by hand: 4*(lane>>4) + reg, lane & 15
+    assert cr.lane_reg_to_row_col(0, 0) == (0, 0)
+    assert cr.lane_reg_to_row_col(15, 3) == (3, 15)
+    assert cr.lane_reg_to_row_col(16, 0) == (4, 0)
+    assert cr.lane_reg_to_row_col(47, 2) == (10, 15)
+    assert cr.lane_reg_to_row_col(63, 3) == (15, 15)
+
+
+def test_expected_bits_are_the_reference_tiles_elements():
+    for fmt in ("bf16", "fp8", "fp4"):
+        ref = cr.reference_tile(fmt, 9, SEEDS[1]).astype(np.float32)
+        for lane, reg in ((0, 0), (15, 1), (16, 2), (47, 3), (63, 3)):
+            row, col = cr.lane_reg_to_row_col(lane, reg)
+            bits = cr.expected_bits(fmt, 9, SEEDS[1], lane, reg)
+            assert np.uint32(bits).view(np.float32) == ref[row, col]
+            assert 0 <= bits <= cr.M32
+
+
+def test_lds_word_known_values():
+    # word 0, seed 0, round 0: fmix32(0) = 0
+    assert cr.lds_word(0, 0, 0) == 0
+    # word 1, seed 0, round 0: fmix32(0x9E3779B9)
+    assert cr.lds_word(1, 0, 0) == 0x92CA2F0E
+    # the last word of 160 KiB, round 2, seed_lo 0xC0FFEE11:
+    # 40959 * 0x9E3779B9 + 0xC0FFEE11 + 2 = 0xCEDC145A (mod 2^32)
+    assert (40959 * 0x9E3779B9 + 0xC0FFEE11 + 2) & cr.M32 == 0xCEDC145A
+    assert cr.lds_word(40959, SEEDS[1], 2) == 0x37C93D0B
+    # seed_hi plays no part; the round does
+    assert cr.lds_word(40959, SEEDS[1] & cr.M32, 2) == 0x37C93D0B
+    assert cr.lds_word(40959, SEEDS[1], 1) != 0x37C93D0B
+
+
+def test_lds_inverted_pattern_is_the_complement():
+    for word in (0, 1, 5, 40959):
+        for rnd in (0, 2):
+            plain = cr.lds_word(word, SEEDS[1], rnd)
+            inv = cr.lds_word(word, SEEDS[1], rnd, inverted=True)
+            assert plain ^ inv == cr.M32 and 0 <= inv <= cr.M32
+
+
+def test_lds_verifiers_are_other_waves_and_lanes_than_the_writer():
+    vecs = 163840 // 16
+    for v in range(vecs):
+        w = cr.lds_writer(4 * v)
+        p0 = cr.lds_verifier(4 * v, 0)
+        p1 = cr.lds_verifier(4 * v, 1)
+        assert w["thread"] == v % 256
+        for a, b in ((w, p0), (w, p1), (p0, p1)):
+            assert a["wave"] != b["wave"] and a["lane"] != b["lane"], v
+        # the four words of a vector share their threads
+        for j in range(1, 4):
+            assert cr.lds_verifier(4 * v + j, 0) == p0 and cr.lds_verifier(4 * v + j, 1) == p1
+    # each thread verifies each residue class exactly once per phase
+    for phase in (0, 1):
+        assert sorted(cr.lds_verifier(4 * v, phase)["thread"] for v in range(256)) == list(range(256))
+    # by hand: vector 0 is read by threads 191 (wave 2, lane 63) and 126 (wave 1, lane 62)
+    assert cr.lds_verifier(0, 0) == {"thread": 191, "wave": 2, "lane": 63}
+    assert cr.lds_verifier(3, 1) == {"thread": 126, "wave": 1, "lane": 62}
+    assert cr.lds_verifier(4 * 65, 0) == {"thread": 0, "wave": 0, "lane": 0}
+
+
 # ---------------------------------------------------------------------------
 # cu_check_fold on synthetic records
 # ---------------------------------------------------------------------------
