@@ -386,15 +386,51 @@ struct DriverResult {
   std::vector<StepRecord> records;
 };
 
+// The driver's steps in run order; an inject entry names one by its index.
+constexpr int kInjectSteps = 6;
+constexpr const char* kStepNames[kInjectSteps] = {
+    "write addr",  "verify addr",      "write rand",
+    "verify rand", "verify_flip rand", "verify rand inverted"};
+constexpr int kDefaultInjectStep = 1;
+
+// Detector self-test: XOR mask into the word at position `word` of the words
+// under test, behind the kernel's back, immediately before step `step`.
+struct Inject {
+  u64 word, mask;
+  int step;
+};
+
+// (word, xor_mask[, step]) entries; needs the GIL.
+std::vector<Inject> parse_inject(const py::sequence& entries) {
+  std::vector<Inject> out;
+  for (py::handle h : entries) {
+    TORCH_CHECK(py::isinstance<py::sequence>(h),
+                "inject: an entry must be (word, xor_mask[, step])");
+    auto e = py::reinterpret_borrow<py::sequence>(h);
+    TORCH_CHECK(e.size() == 2 || e.size() == 3,
+                "inject: an entry must be (word, xor_mask[, step]), got ",
+                e.size(), " elements");
+    Inject in{e[0].cast<u64>(), e[1].cast<u64>(), kDefaultInjectStep};
+    if (e.size() == 3) {
+      long long step = e[2].cast<long long>();
+      TORCH_CHECK(step >= 0 && step < kInjectSteps, "inject: step ", step,
+                  " is outside 0..", kInjectSteps - 1);
+      in.step = (int)step;
+    }
+    out.push_back(in);
+  }
+  return out;
+}
+
 DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
                         u64 seed, u64 cap, bool scrub,
-                        const std::vector<std::pair<u64, u64>>& inject) {
+                        const std::vector<Inject>& inject, u64 base_word) {
   DriverResult out;
   u64 total_words = 0;
   for (u64 w : chunk_words) total_words += w;
   out.bytes = total_words * 8;
   for (auto& in : inject)
-    TORCH_CHECK(in.first < total_words, "inject: word ", in.first,
+    TORCH_CHECK(in.word < total_words, "inject: word ", in.word,
                 " is outside the ", total_words, " words under test");
 
   DeviceScope scope(device);
@@ -411,11 +447,25 @@ DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
   // One step = one mode over ALL chunks: with >= 1 GiB under test every line
   // has left the 256 MiB Infinity Cache before the next step reads it, so
   // the read-back comes from HBM.
+  int steps_run = 0;
   auto step = [&](const char* name, int mode, int pat, bool invert) {
+    // every earlier step has ended with stream.synchronize()
+    for (auto& in : inject) {
+      if (in.step != steps_run) continue;
+      u64 off = 0;
+      size_t c = 0;
+      while (in.word - off >= chunk_words[c]) off += chunk_words[c++];
+      u64* addr = chunks[c].ptr + (in.word - off);
+      u64 word = 0;
+      HIP_CHECK(hipMemcpy(&word, addr, 8, hipMemcpyDeviceToHost));
+      word ^= in.mask;
+      HIP_CHECK(hipMemcpy(addr, &word, 8, hipMemcpyHostToDevice));
+    }
+    ++steps_run;
     if (mode != kWrite)
       HIP_CHECK(hipMemsetAsync(rep.ptr, 0, rep_words * 8, stream.s));
     t0.record(stream);
-    u64 g = 0;
+    u64 g = base_word;
     for (size_t i = 0; i < chunks.size(); ++i) {
       launch(mode, pat, chunks[i].ptr, chunk_words[i], g, seed, invert, rep.ptr,
              cap, stream.s);
@@ -442,23 +492,12 @@ DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
     }
   };
 
-  step("write addr", kWrite, kAddr, false);
-  // detector self-test: flip bits behind the kernel's back
-  for (auto& in : inject) {
-    u64 g = in.first, off = 0;
-    size_t c = 0;
-    while (g - off >= chunk_words[c]) off += chunk_words[c++];
-    u64* addr = chunks[c].ptr + (g - off);
-    u64 word = 0;
-    HIP_CHECK(hipMemcpy(&word, addr, 8, hipMemcpyDeviceToHost));
-    word ^= in.second;
-    HIP_CHECK(hipMemcpy(addr, &word, 8, hipMemcpyHostToDevice));
-  }
-  step("verify addr", kVerify, kAddr, false);
-  step("write rand", kWrite, kRand, false);
-  step("verify rand", kVerify, kRand, false);
-  step("verify_flip rand", kVerifyFlip, kRand, false);
-  step("verify rand inverted", kVerify, kRand, true);
+  step(kStepNames[0], kWrite, kAddr, false);
+  step(kStepNames[1], kVerify, kAddr, false);
+  step(kStepNames[2], kWrite, kRand, false);
+  step(kStepNames[3], kVerify, kRand, false);
+  step(kStepNames[4], kVerifyFlip, kRand, false);
+  step(kStepNames[5], kVerify, kRand, true);
   if (scrub) step("scrub", kWrite, kZero, false);
 
   w1.record(stream);
@@ -467,10 +506,15 @@ DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
   return out;
 }
 
+// inject entries are (word, xor_mask[, step]): word is a position within the
+// words under test, step the index into kStepNames of the step the flip comes
+// immediately before (two elements mean "verify addr"). base_word is the g of
+// the first chunk's first word; a record's g is base_word + position.
 py::dict hbm_memtest(int device, std::vector<u64> chunk_bytes, u64 seed,
                      long long max_records, bool scrub,
-                     std::vector<std::pair<u64, u64>> inject) {
+                     const py::sequence& inject_entries, u64 base_word) {
   u64 cap = check_max_records(max_records);
+  const std::vector<Inject> inject = parse_inject(inject_entries);
   int ndev = 0;
   HIP_CHECK(hipGetDeviceCount(&ndev));
   TORCH_CHECK(device >= 0 && device < ndev, "no such device ", device);
@@ -484,7 +528,7 @@ py::dict hbm_memtest(int device, std::vector<u64> chunk_bytes, u64 seed,
   DriverResult r;
   {
     py::gil_scoped_release release;
-    r = run_driver(device, words, seed, cap, scrub, inject);
+    r = run_driver(device, words, seed, cap, scrub, inject, base_word);
   }
   py::dict d;
   d["bytes_tested"] = py::int_(r.bytes);

@@ -878,9 +878,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("memtest_geometry", &hbm_memtest::memtest_geometry);
   m.def("hbm_memtest", &hbm_memtest::hbm_memtest, py::arg("device"),
         py::arg("chunk_bytes"), py::arg("seed"), py::arg("max_records") = 32,
-        py::arg("scrub") = false,
-        py::arg("inject") =
-            std::vector<std::pair<unsigned long long, unsigned long long>>{});
+        py::arg("scrub") = false, py::arg("inject") = py::list(),
+        py::arg("base_word") = 0);
   m.def("cu_check", &cu_check::cu_check, py::arg("device"), py::arg("rounds"),
         py::arg("seed"), py::arg("grid_mult") = 2,
         py::arg("inject") = std::vector<std::vector<long long>>{});

@@ -12,7 +12,13 @@ Word g (a global u64 index) holds, for a u64 seed:
           w  = hi<<32 | lo
     zero: w = 0
     invert: w = ~w
+
+word_class names who handles a word of a view in the kernel (tile, trip,
+workgroup, wave, lane, unroll slot, half of the 16-byte vector), so that a
+failing GPU assertion says which part of the kernel missed it.
 """
+from typing import NamedTuple
+
 import numpy as np
 
 SEED = 0x0123456789ABCDEF
@@ -29,6 +35,59 @@ GOLDEN_RAND = [
     (2**32 + 1, 0xDA90EBAAEA16BC8C),
     (2**40 + 7, 0xE26A43E94606D2BC),
 ]
+
+
+# memtest_geometry() of the kernel as committed; the GPU tests read the
+# binding and hold it to this
+GEOMETRY = {"block": 256, "words_per_thread_iter": 8, "max_grid": 2048}
+
+
+class WordClass(NamedTuple):
+    """Who handles one body word of a view (csrc/hbm_memtest.hip)."""
+    tile: int       # index of the block * unroll vectors it lies in
+    trip: int       # iteration of the workgroup's grid-stride loop
+    workgroup: int  # blockIdx.x
+    wave: int
+    lane: int
+    slot: int       # unroll slot j of the tile loop
+    half: int       # 0: .x of the 16-byte vector, 1: .y
+    full: bool      # the tile takes the unrolled path, not the bounds-checked one
+
+
+def word_class(p: int, head: int, n: int, geo=GEOMETRY):
+    """Position p of an n-word view -> "head", "tail" or a WordClass.
+
+    head is 1 for a view that is only 8-byte aligned (its first word is
+    handled alone by thread 0 of workgroup 0) and 0 for a 16-byte-aligned
+    one; a tail word exists where n - head is odd (thread 1 of workgroup 0).
+    The rest is the body: vector vi = (p - head) // 2 belongs to tile
+    vi // (block * unroll), where thread vi % block handles it in unroll slot
+    (vi % (block * unroll)) // block, and tile t runs in workgroup
+    t % max_grid on trip t // max_grid."""
+    if head not in (0, 1):
+        raise ValueError(f"head must be 0 or 1, got {head}")
+    if not 0 <= p < n:
+        raise ValueError(f"position {p} is outside a view of {n} words")
+    if head and p == 0:
+        return "head"
+    if (n - head) % 2 == 1 and p == n - 1:
+        return "tail"
+    block = geo["block"]
+    tile_vecs = block * (geo["words_per_thread_iter"] // 2)
+    vi = (p - head) // 2
+    tile, within = divmod(vi, tile_vecs)
+    slot, thread = divmod(within, block)
+    nvec = (n - head) // 2
+    return WordClass(
+        tile=tile,
+        trip=tile // geo["max_grid"],
+        workgroup=tile % geo["max_grid"],
+        wave=thread // 64,
+        lane=thread % 64,
+        slot=slot,
+        half=(p - head) % 2,
+        full=(tile + 1) * tile_vecs <= nvec,
+    )
 
 
 def to_i64(v: int) -> int:

@@ -62,6 +62,85 @@ def test_references_agree(pattern, invert, base):
 
 
 # ---------------------------------------------------------------------------
+# word_class: which tile, workgroup, wave, lane, slot and half owns a word
+# ---------------------------------------------------------------------------
+
+GEO = mr.GEOMETRY
+T = GEO["block"] * GEO["words_per_thread_iter"]
+W = T * GEO["max_grid"]
+
+
+@pytest.mark.parametrize("head", [0, 1])
+def test_word_class_is_a_bijection_on_a_tile(head):
+    """The 2048 body words of a tile map one to one onto 4 waves x 64 lanes x
+    4 slots x 2 halves, for a full first-trip tile, a second-trip tile and
+    the tile before the bounds-checked one."""
+    n = W + 2 * T + 5
+    for tile in (0, 1, GEO["max_grid"], GEO["max_grid"] + 1):
+        seen = set()
+        for p in range(head + tile * T, head + (tile + 1) * T):
+            c = mr.word_class(p, head, n, GEO)
+            assert c.tile == tile and c.full
+            assert c.workgroup == tile % GEO["max_grid"]
+            assert c.trip == tile // GEO["max_grid"]
+            seen.add((c.wave, c.lane, c.slot, c.half))
+        assert len(seen) == T
+        assert seen == {(w, l, s, h) for w in range(4) for l in range(64)
+                        for s in range(4) for h in range(2)}
+    # one vector is one (wave, lane, slot); consecutive vectors are
+    # consecutive lanes: the coalesced 16 B per lane of the header
+    a, b, c = (mr.word_class(head + q, head, n, GEO) for q in (0, 1, 2))
+    assert a[:6] == b[:6] and (a.half, b.half) == (0, 1)
+    assert (c.lane, c.slot, c.half) == (1, 0, 0)
+
+
+def test_word_class_head_and_tail():
+    # n = 0: no position at all
+    for head in (0, 1):
+        with pytest.raises(ValueError):
+            mr.word_class(0, head, 0, GEO)
+    # n = 1: the one word is the tail of an aligned view, the head of an odd one
+    assert mr.word_class(0, 0, 1, GEO) == "tail"
+    assert mr.word_class(0, 1, 1, GEO) == "head"
+    # n = 2: one vector, or head and tail with no body between them
+    assert [mr.word_class(p, 0, 2, GEO) for p in (0, 1)] == [
+        (0, 0, 0, 0, 0, 0, 0, False), (0, 0, 0, 0, 0, 0, 1, False)]
+    assert [mr.word_class(p, 1, 2, GEO) for p in (0, 1)] == ["head", "tail"]
+    # the views of the GPU tests: a tail exists exactly where n - head is odd
+    for head, n, tail in ((0, 3 * T + 5, True), (1, 3 * T + 6, True),
+                          (0, 3 * T + 6, False), (1, 3 * T + 5, False)):
+        classes = [mr.word_class(p, head, n, GEO) for p in range(n)]
+        assert (classes[0] == "head") == bool(head)
+        assert (classes[-1] == "tail") == tail
+        body = classes[head : n - 1 if tail else n]
+        assert "head" not in body and "tail" not in body
+        assert len(body) % 2 == 0
+    with pytest.raises(ValueError):
+        mr.word_class(5, 0, 5, GEO)
+    with pytest.raises(ValueError):
+        mr.word_class(-1, 0, 5, GEO)
+    with pytest.raises(ValueError):
+        mr.word_class(0, 2, 5, GEO)
+
+
+def test_word_class_by_hand():
+    assert (T, W) == (2048, 4194304)
+    # aligned, n = 6150 (3075 vectors): p = 4097 is .y of vector 2048, the
+    # first vector of tile 2; 3 * 1024 <= 3075, so tile 2 is full
+    assert mr.word_class(4097, 0, 6150, GEO) == (2, 0, 2, 0, 0, 0, 1, True)
+    # odd view, n = 6150: 6149 body-and-tail words, the last is the tail;
+    # p = 6148 is body word 6147, .y of vector 3073 = tile 3, thread 1 of
+    # slot 0; 3074 vectors < 4 * 1024, so tile 3 is bounds-checked
+    assert mr.word_class(6149, 1, 6150, GEO) == "tail"
+    assert mr.word_class(6148, 1, 6150, GEO) == (3, 0, 3, 0, 1, 0, 1, False)
+    # odd view, n = W + 2T + 5: vector 2048 * 1024 + 3 * 256 + 191 is tile
+    # 2048 (workgroup 0 on its second trip), slot 3, thread 191 = wave 2
+    # lane 63; its .x is p = 1 + 2 * 2098111
+    assert mr.word_class(4196223, 1, W + 2 * T + 5, GEO) == (
+        2048, 1, 0, 2, 63, 3, 0, True)
+
+
+# ---------------------------------------------------------------------------
 # memtest_plan
 # ---------------------------------------------------------------------------
 
@@ -209,6 +288,19 @@ def test_validate_memtest_skipped_leaves_throughput_rule(stub):
     assert g["memtest"] == {"skipped": "insufficient free HBM"}
     assert ext.memtest_calls == []
     assert g["healthy"] is True
+
+
+def test_memtest_gpu_forwards_two_element_inject_entries(stub):
+    """The binding's optional third inject field and its base_word keyword
+    are for the tests: memtest_gpu passes what it always passed."""
+    from gpu_docker_api_amd.ops import hipcore
+
+    ext = stub()
+    inject = [(12345, 0x8000000000000001), (7, 1)]
+    hipcore.memtest_gpu(0, 2048, inject=inject)
+    assert len(ext.memtest_calls) == 1  # six positional arguments, no keyword
+    assert ext.memtest_calls[0][5] == inject
+    assert all(type(e) is tuple and len(e) == 2 for e in ext.memtest_calls[0][5])
 
 
 # ---------------------------------------------------------------------------
