@@ -60,25 +60,27 @@
 // out and is then 0. Entries change values only, never an address; the host
 // rejects entries out of range and the kernel bounds the LDS word again.
 //
-// Included by hipcore.hip (needs the torch headers, hip_host.h for HIP_CHECK
-// and the resource owners the driver holds, and hbm_memtest.hip's fmix32).
+// fmix32 and the generator's elem_code / elem_int are in burnin_core.h, where
+// burnin_selftest.cpp runs them on the CPU; this check draws every format at
+// its full range (bf16 127, e4m3 4, e2m1 16).
+//
+// Included by hipcore.hip (needs the torch headers and hipcore.hip's
+// using-declarations of hip_host.h's resource owners).
+#include "burnin_core.h"
+#include "burnin_host.h"
 
 namespace cu_check {
 
-using u32 = unsigned int;
-using u64 = unsigned long long;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+using namespace burnin;
 using i32x8 = __attribute__((ext_vector_type(8))) int;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using hbm_memtest::fmix32;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr u32 kGolden = 0x9E3779B9u;
 
-enum Test { kBf16 = 0, kFp8 = 1, kFp4 = 2, kLds = 3, kNumTests = 4 };
-constexpr int kK[3] = {1024, 1152, 1280};
+// The three formats, then the LDS test.
+constexpr int kLds = kNumFormats, kNumTests = kNumFormats + 1;
+constexpr int kK[kNumFormats] = {1024, 1152, 1280};
 const char* const kTestNames[kNumTests] = {"bf16", "fp8", "fp4", "lds"};
 
 // One wave's sub-record, u32 words. kRecFirstTest holds test + 1, 0 = none.
@@ -97,50 +99,20 @@ constexpr int kMaxGridMult = 8;
 constexpr int kMaxLaunches = 8;
 constexpr int kMaxTile = kMaxRounds * kWaves;
 
-__device__ inline u32 tile_base(u32 seed_lo, u32 seed_hi, u32 t) {
-  return fmix32(seed_lo + t * kGolden) ^ seed_hi;
-}
-
 template <int FMT>
 __device__ __forceinline__ u32 gen(u32 base, u32 operand, u32 row, u32 k) {
   return fmix32(base ^ ((u32)FMT << 28 | operand << 20 | row << 12 | k));
 }
 
-// The element as the MFMA wants it: bf16 bits, e4m3 byte or e2m1 nibble.
+// The element of draw u as the MFMA wants it, and as an integer count of
+// operand granules: the generator at the format's full range.
 template <int FMT>
-__device__ __forceinline__ u32 elem_code(u32 u) {
-  if (FMT == kBf16) {
-    int m = (int)(u % 255u) - 127;
-    return __builtin_bit_cast(u32, (float)m * 0.0625f) >> 16;  // 7 bits: exact
-  }
-  if (FMT == kFp8) {
-    u32 j = u % 65u;
-    u32 q = j - 1u;
-    return j == 0 ? 0u : ((q >> 5) << 7 | (6u + ((q & 31u) >> 3)) << 3 | (q & 7u));
-  }
-  return u & 15u;
+__device__ __forceinline__ u32 code(u32 u) {
+  return elem_code<FMT, kFullRange[FMT]>(u);
 }
-
-// The same element as an integer count of granules (1/16, 2^-4, 1/2), from
-// the generator's definition and not from the code above.
 template <int FMT>
-__device__ __forceinline__ int elem_int(u32 u) {
-  if (FMT == kBf16) return (int)(u % 255u) - 127;
-  if (FMT == kFp8) {
-    u32 j = u % 65u;
-    if (j == 0) return 0;
-    u32 q = j - 1u;
-    int mag = (int)((8u + (q & 7u)) << ((q & 31u) >> 3));  // (1+m/8) * 2^(e-7) * 16
-    return (q >> 5) ? -mag : mag;
-  }
-  u32 e = (u >> 1) & 3u, m = u & 1u;
-  int mag = e == 0 ? (int)m : (int)((2u + m) << (e - 1u));  // (1+m/2) * 2^(e-1) * 2
-  return (u & 8u) ? -mag : mag;
-}
-
-template <int FMT>
-__device__ inline float granule_sq() {
-  return FMT == kFp4 ? 0.25f : 1.0f / 256.0f;
+__device__ __forceinline__ int numer(u32 u) {
+  return elem_int<FMT, kFullRange[FMT]>(u);
 }
 
 // The MFMA chain of one tile, one wave.
@@ -156,10 +128,10 @@ __device__ __forceinline__ f32x4 mfma_tile(u32 base, int lane) {
       u32x4 a, b;
 #pragma unroll
       for (u32 j = 0; j < 4; ++j) {
-        a[j] = elem_code<FMT>(gen<FMT>(base, 0, row, k0 + 2 * j)) |
-               elem_code<FMT>(gen<FMT>(base, 0, row, k0 + 2 * j + 1)) << 16;
-        b[j] = elem_code<FMT>(gen<FMT>(base, 1, row, k0 + 2 * j)) |
-               elem_code<FMT>(gen<FMT>(base, 1, row, k0 + 2 * j + 1)) << 16;
+        a[j] = code<FMT>(gen<FMT>(base, 0, row, k0 + 2 * j)) |
+               code<FMT>(gen<FMT>(base, 0, row, k0 + 2 * j + 1)) << 16;
+        b[j] = code<FMT>(gen<FMT>(base, 1, row, k0 + 2 * j)) |
+               code<FMT>(gen<FMT>(base, 1, row, k0 + 2 * j + 1)) << 16;
       }
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
           __builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0,
@@ -175,8 +147,8 @@ __device__ __forceinline__ f32x4 mfma_tile(u32 base, int lane) {
         u32 wa = 0, wb = 0;
 #pragma unroll
         for (u32 j = 0; j < 4; ++j) {
-          wa |= elem_code<FMT>(gen<FMT>(base, 0, row, k0 + 4 * d + j)) << (8 * j);
-          wb |= elem_code<FMT>(gen<FMT>(base, 1, row, k0 + 4 * d + j)) << (8 * j);
+          wa |= code<FMT>(gen<FMT>(base, 0, row, k0 + 4 * d + j)) << (8 * j);
+          wb |= code<FMT>(gen<FMT>(base, 1, row, k0 + 4 * d + j)) << (8 * j);
         }
         a[d] = (int)wa;
         b[d] = (int)wb;
@@ -194,8 +166,8 @@ __device__ __forceinline__ f32x4 mfma_tile(u32 base, int lane) {
         u32 wa = 0, wb = 0;
 #pragma unroll
         for (u32 j = 0; j < 8; ++j) {
-          wa |= elem_code<FMT>(gen<FMT>(base, 0, row, k0 + 8 * d + j)) << (4 * j);
-          wb |= elem_code<FMT>(gen<FMT>(base, 1, row, k0 + 8 * d + j)) << (4 * j);
+          wa |= code<FMT>(gen<FMT>(base, 0, row, k0 + 8 * d + j)) << (4 * j);
+          wb |= code<FMT>(gen<FMT>(base, 1, row, k0 + 8 * d + j)) << (4 * j);
         }
         a[d] = (int)wa;
         b[d] = (int)wb;
@@ -215,14 +187,14 @@ __device__ __forceinline__ f32x4 expect_tile(u32 base, int lane) {
   int sum[4] = {0, 0, 0, 0};
 #pragma unroll 2
   for (u32 k = 0; k < (u32)kK[FMT]; ++k) {
-    const int b = elem_int<FMT>(gen<FMT>(base, 1, col, k));
+    const int b = numer<FMT>(gen<FMT>(base, 1, col, k));
 #pragma unroll
     for (u32 r = 0; r < 4; ++r)
-      sum[r] += elem_int<FMT>(gen<FMT>(base, 0, row0 + r, k)) * b;
+      sum[r] += numer<FMT>(gen<FMT>(base, 0, row0 + r, k)) * b;
   }
   f32x4 e;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) e[r] = (float)sum[r] * granule_sq<FMT>();
+  for (int r = 0; r < 4; ++r) e[r] = (float)sum[r] * (1.0f / kInvGranule[FMT]);
   return e;
 }
 
@@ -251,7 +223,7 @@ template <int FMT>
 __device__ __forceinline__ void check_tile(
     LaneState& st, u32 seed_lo, u32 seed_hi, u32 round, u32 t, int lane,
     const u32* __restrict__ inject, int n_inject) {
-  const u32 base = tile_base(seed_lo, seed_hi, t);
+  const u32 base = key_base(seed_lo, seed_hi, t);
   f32x4 acc = mfma_tile<FMT>(base, lane);
   for (int i = 0; i < n_inject; ++i) {
     const u32* e = inject + kInjectWords * i;
@@ -388,7 +360,7 @@ template <int FMT>
 __global__ __launch_bounds__(64) void cu_check_tile_kernel(
     float* __restrict__ out, u32 seed_lo, u32 seed_hi, u32 t) {
   const int lane = threadIdx.x & 63;
-  const f32x4 acc = mfma_tile<FMT>(tile_base(seed_lo, seed_hi, t), lane);
+  const f32x4 acc = mfma_tile<FMT>(key_base(seed_lo, seed_hi, t), lane);
   const int col = lane & 15;
   const int row0 = (lane >> 4) * 4;
 #pragma unroll
@@ -410,12 +382,12 @@ torch::Tensor cu_check_tile(const std::string& fmt, long long tile, u64 seed) {
       {16, 16}, torch::TensorOptions().dtype(torch::kFloat32).device(torch::kCUDA));
   auto stream = at::hip::getCurrentHIPStream();
   float* p = out.data_ptr<float>();
-  const u32 lo = (u32)seed, hi = (u32)(seed >> 32), t = (u32)tile;
+  const SeedHalves s = split_seed(seed);
   constexpr void (*kTileKernels[3])(float*, u32, u32, u32) = {
       cu_check_tile_kernel<kBf16>, cu_check_tile_kernel<kFp8>,
       cu_check_tile_kernel<kFp4>};
   hipLaunchKernelGGL(kTileKernels[f], dim3(1), dim3(64), 0, stream.stream(), p,
-                     lo, hi, t);
+                     s.lo, s.hi, (u32)tile);
   HIP_CHECK(hipGetLastError());
   return out;
 }
@@ -530,12 +502,13 @@ DriverResult run_driver(int device, int rounds, u64 seed, int grid_mult,
   std::vector<u32> host(rec_words);
   std::vector<bool> seen(1u << 12, false);
   int distinct = 0;
+  const SeedHalves sd = split_seed(seed);
   // On an idle GPU the first launch covers every CU; a busy one may need more.
   while (out.launches < kMaxLaunches) {
     HIP_CHECK(hipMemsetAsync(rec.ptr, 0, rec_bytes, stream.s));
     hipLaunchKernelGGL(cu_check_kernel, dim3(out.grid), dim3(kThreads),
-                       out.lds_bytes, stream.s, rec.ptr, rounds, (u32)seed,
-                       (u32)(seed >> 32), lds_vecs, inj.ptr, (int)inject.size());
+                       out.lds_bytes, stream.s, rec.ptr, rounds, sd.lo, sd.hi,
+                       lds_vecs, inj.ptr, (int)inject.size());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(host.data(), rec.ptr, rec_bytes,
                              hipMemcpyDeviceToHost, stream.s));
@@ -563,9 +536,7 @@ DriverResult run_driver(int device, int rounds, u64 seed, int grid_mult,
 
 py::dict cu_check(int device, int rounds, u64 seed, int grid_mult,
                   std::vector<std::vector<long long>> inject) {
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  TORCH_CHECK(device >= 0 && device < ndev, "no such device ", device);
+  check_device(device);
   TORCH_CHECK(rounds >= 1 && rounds <= kMaxRounds, "rounds must be in [1, ",
               kMaxRounds, "]");
   TORCH_CHECK(grid_mult >= 0 && grid_mult <= kMaxGridMult,

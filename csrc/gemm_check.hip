@@ -67,33 +67,29 @@
 // Report, device-resident u64 words: [0] row mismatches, [1] column
 // mismatches, [2] malformed elements, [3] record slots claimed, [4] operand
 // elements that differ from the generator, then up to cap records of
-// kRecWords words, claimed as hbm_memtest.hip claims its slots. Counts are
-// never capped.
+// kRecWords words, claimed with burnin_core.h's claim_record. Counts are never
+// capped.
 //
 // No spin-waits, nothing shared between workgroups but the counters; every
 // kernel ends by itself whatever it finds.
 //
+// fmix32, the generator's elem_code / elem_int and the exactness condition
+// are in burnin_core.h, where burnin_selftest.cpp runs them on the CPU.
+//
 // Included by hipcore.hip after its 256^2 variant tables (needs the torch
-// headers, hip_host.h, hbm_memtest.hip's fmix32, find_variant and launch_256).
+// headers, hipcore.hip's using-declarations of hip_host.h's resource owners,
+// mfma_warmup, find_variant and launch_256).
+#include "burnin_core.h"
+#include "burnin_host.h"
 
 namespace gemm_check {
 
-using u32 = unsigned int;
-using u64 = unsigned long long;
-using i64 = long long;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
-using hbm_memtest::fmix32;
+using namespace burnin;
 
-enum Kind { kBf16 = 0, kFp8 = 1, kFp4 = 2, kNumKinds = 3 };
-const char* const kKindNames[kNumKinds] = {"bf16", "fp8", "fp4"};
-constexpr int kElemBits[kNumKinds] = {16, 8, 4};
-constexpr int kMinK[kNumKinds] = {192, 256, 512};      // the GEMM bindings'
-constexpr int kKMult[kNumKinds] = {64, 128, 256};
-constexpr int kDefaultCode[kNumKinds] = {0, 16, 16};   // what validate_gpus times
-constexpr float kInvGranule[kNumKinds] = {256.f, 256.f, 4.f};
-constexpr i64 kTwo24 = 1ll << 24;
-constexpr u32 kGolden = 0x9E3779B9u;
+// A kind is one of burnin_core.h's formats.
+constexpr int kMinK[kNumFormats] = {192, 256, 512};      // the GEMM bindings'
+constexpr int kKMult[kNumFormats] = {64, 128, 256};
+constexpr int kDefaultCode[kNumFormats] = {0, 16, 16};   // what validate_gpus times
 
 constexpr int kTile = 256;
 constexpr int kThreads = 256;
@@ -111,7 +107,6 @@ constexpr int kRepRows = 0, kRepCols = 1, kRepMalformed = 2, kRepClaimed = 3,
 constexpr int kRecWords = 5;
 enum RecType { kRecRow = 0, kRecCol = 1, kRecMalformed = 2 };
 const char* const kRecTypeNames[3] = {"row", "col", "malformed"};
-constexpr u64 kMaxRecordsLimit = 65536;
 constexpr int kMaxInject = 64;
 constexpr int kMaxIters = 100000;
 constexpr int kMaxExtent = 1 << 16;
@@ -136,45 +131,9 @@ constexpr int kDefaultLoop = kSerial;
 // Generator
 // ---------------------------------------------------------------------------
 
-__device__ __forceinline__ u32 row_base(u32 seed_lo, u32 seed_hi, u32 row) {
-  return fmix32(seed_lo + row * kGolden) ^ seed_hi;
-}
-
 template <int KIND>
 __device__ __forceinline__ u32 draw(u32 base, u32 operand, u32 k) {
   return fmix32(base ^ ((u32)KIND << 28 | operand << 24 | k));
-}
-
-// The element as the GEMM wants it: bf16 bits, e4m3 byte or e2m1 nibble.
-template <int KIND>
-__device__ __forceinline__ u32 elem_code(u32 u, u32 range) {
-  if (KIND == kBf16) {
-    int m = (int)(u % (2u * range + 1u)) - (int)range;
-    return __builtin_bit_cast(u32, (float)m * 0.0625f) >> 16;  // 7 bits: exact
-  }
-  if (KIND == kFp8) {
-    u32 j = u % (16u * range + 1u);
-    u32 q = j - 1u, s = q / (8u * range), t = q % (8u * range);
-    return j == 0 ? 0u : (s << 7 | (6u + (t >> 3)) << 3 | (t & 7u));
-  }
-  return u & 15u;
-}
-
-// The same element as an integer count of granules (1/16, 2^-4, 1/2), from
-// the generator's definition and not from the code above.
-template <int KIND>
-__device__ __forceinline__ int elem_int(u32 u, u32 range) {
-  if (KIND == kBf16) return (int)(u % (2u * range + 1u)) - (int)range;
-  if (KIND == kFp8) {
-    u32 j = u % (16u * range + 1u);
-    if (j == 0) return 0;
-    u32 q = j - 1u, s = q / (8u * range), t = q % (8u * range);
-    int mag = (int)((8u + (t & 7u)) << (t >> 3));  // (1+m/8) * 2^(e-7) * 16
-    return s ? -mag : mag;
-  }
-  u32 e = (u >> 1) & 3u, m = u & 1u;
-  int mag = e == 0 ? (int)m : (int)((2u + m) << (e - 1u));  // (1+m/2) * 2^(e-1) * 2
-  return (u & 8u) ? -mag : mag;
 }
 
 // Operand fill, or with CHECK the comparison of a stored operand with the
@@ -192,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void operand_kernel(
   for (u64 v = (u64)blockIdx.x * kThreads + threadIdx.x; v < nvec; v += stride) {
     const u32 row = (u32)(v / vecs_per_row);
     const u32 k0 = (u32)(v % vecs_per_row) * 4u * kPerWord;
-    const u32 base = row_base(seed_lo, seed_hi, row);
+    const u32 base = key_base(seed_lo, seed_hi, row);
     u32x4 e;
 #pragma unroll
     for (u32 w = 0; w < 4; ++w) {
@@ -218,8 +177,7 @@ __global__ __launch_bounds__(kThreads) void operand_kernel(
     }
   }
   if (CHECK) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off, 64);
+    wave_sum(bad);
     if ((threadIdx.x & 63) == 0 && bad != 0) atomicAdd(&rep[kRepOperand], (u64)bad);
   }
 }
@@ -239,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void tile_sum_kernel(
   int s = 0;
   for (u32 r = 0; r < (u32)kTile; ++r)
     s += elem_int<KIND>(
-        draw<KIND>(row_base(seed_lo, seed_hi, t * kTile + r), operand, k), range);
+        draw<KIND>(key_base(seed_lo, seed_hi, t * kTile + r), operand, k), range);
   S[idx] = s;
 }
 
@@ -253,7 +211,7 @@ __global__ __launch_bounds__(kThreads) void row_dot_kernel(
   const u32 lane = threadIdx.x & 63;
   const u32 row = blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (row >= rows) return;  // wave-uniform
-  const u32 base = row_base(seed_lo, seed_hi, row);
+  const u32 base = key_base(seed_lo, seed_hi, row);
   for (u32 t0 = 0; t0 < tiles; t0 += kDotTiles) {
     i64 acc[kDotTiles];
 #pragma unroll
@@ -279,18 +237,12 @@ __global__ __launch_bounds__(kThreads) void row_dot_kernel(
 // Verify
 // ---------------------------------------------------------------------------
 
-// Mismatch slow path: one claim per finding, and only while the claim counter
-// is below the cap (hbm_memtest::record_mismatch).
+// Mismatch slow path: one claimed record per finding while slots are left.
 __device__ __noinline__ void record(u64* rep, u64 cap, u64 type, u64 iter,
                                     u64 tile_row, u64 tile_col, u64 index,
                                     u64 got, u64 want) {
-  if (cap == 0) return;
-  u64 claimed = __hip_atomic_load(&rep[kRepClaimed], __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_AGENT);
-  if (claimed >= cap) return;
-  u64 slot = atomicAdd(&rep[kRepClaimed], 1ull);
-  if (slot >= cap) return;
-  u64* r = rep + kRepHeader + kRecWords * slot;
+  u64* r;
+  if (!claim_record<kRepClaimed, kRepHeader, kRecWords>(rep, cap, r)) return;
   r[0] = type | iter << 8;
   r[1] = tile_row << 32 | tile_col;
   r[2] = index;
@@ -368,8 +320,7 @@ __global__ __launch_bounds__(kThreads) void verify_kernel(
   else
     slab[((size_t)tile * kStrips + strip) * kTile + threadIdx.x] = sum;
 
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off, 64);
+  wave_sum(bad);
   if (lane == 0 && bad != 0) atomicAdd(&rep[kRepMalformed], (u64)bad);
 }
 
@@ -410,8 +361,8 @@ __global__ void inject_kernel(float* C, size_t element, u32 mask) {
 // ---------------------------------------------------------------------------
 
 int parse_kind(const std::string& name) {
-  for (int i = 0; i < kNumKinds; ++i)
-    if (name == kKindNames[i]) return i;
+  for (int i = 0; i < kNumFormats; ++i)
+    if (name == kFormatNames[i]) return i;
   TORCH_CHECK(false, "gemm_check: unknown kind '", name, "' (bf16, fp8, fp4)");
   return -1;
 }
@@ -420,19 +371,17 @@ int parse_kind(const std::string& name) {
 // must not exceed 2^24.
 void check_range(int kind, i64 K, i64 range) {
   TORCH_CHECK(K >= 1 && K <= kTwo24, "gemm_check: K must be in [1, 2^24]");
-  i64 top = 0;
+  const bool legal = range >= kMinRange[kind] && range <= kFullRange[kind];
   if (kind == kBf16) {
-    TORCH_CHECK(range >= 1 && range <= 127, "gemm_check: bf16 range must be in [1, 127]");
-    top = range;
+    TORCH_CHECK(legal, "gemm_check: bf16 range must be in [1, 127]");
   } else if (kind == kFp8) {
-    TORCH_CHECK(range >= 1 && range <= 4, "gemm_check: fp8 range must be in [1, 4]");
-    top = 15ll << (range - 1);
+    TORCH_CHECK(legal, "gemm_check: fp8 range must be in [1, 4]");
   } else {
-    TORCH_CHECK(range == 16, "gemm_check: fp4 range must be 16");
-    top = 12;
+    TORCH_CHECK(legal, "gemm_check: fp4 range must be 16");
   }
-  TORCH_CHECK(top * top * K <= kTwo24, "gemm_check: range ", range, " of ",
-              kKindNames[kind], " is not exact at K = ", K, ": ", top, "^2 * K > 2^24");
+  TORCH_CHECK(sums_exact(kind, range, K), "gemm_check: range ", range, " of ",
+              kFormatNames[kind], " is not exact at K = ", K, ": ",
+              max_numerator(kind, range), "^2 * K > 2^24");
 }
 
 void check_extent(i64 v, const char* name) {
@@ -443,14 +392,8 @@ void check_extent(i64 v, const char* name) {
 // K as the kind's GEMM binding takes it.
 void check_k(int kind, i64 K) {
   TORCH_CHECK(K >= kMinK[kind] && K % kKMult[kind] == 0, "gemm_check: K of ",
-              kKindNames[kind], " must be a multiple of ", kKMult[kind], ", >= ",
+              kFormatNames[kind], " must be a multiple of ", kKMult[kind], ", >= ",
               kMinK[kind]);
-}
-
-u64 check_max_records(i64 max_records) {
-  TORCH_CHECK(max_records >= 0 && (u64)max_records <= kMaxRecordsLimit,
-              "max_records must be in [0, ", kMaxRecordsLimit, "]");
-  return (u64)max_records;
 }
 
 size_t operand_bytes(int kind, size_t rows, size_t K) {
@@ -458,17 +401,17 @@ size_t operand_bytes(int kind, size_t rows, size_t K) {
 }
 
 using OperandKernel = void (*)(u32x4*, u64, u32, u32, u32, u32, u32, u64*);
-constexpr OperandKernel kOperandKernels[kNumKinds][2] = {
+constexpr OperandKernel kOperandKernels[kNumFormats][2] = {
     {operand_kernel<kBf16, false>, operand_kernel<kBf16, true>},
     {operand_kernel<kFp8, false>, operand_kernel<kFp8, true>},
     {operand_kernel<kFp4, false>, operand_kernel<kFp4, true>},
 };
 using TileSumKernel = void (*)(int*, u32, u32, u32, u32, u32, u32);
-constexpr TileSumKernel kTileSumKernels[kNumKinds] = {
+constexpr TileSumKernel kTileSumKernels[kNumFormats] = {
     tile_sum_kernel<kBf16>, tile_sum_kernel<kFp8>, tile_sum_kernel<kFp4>};
 using RowDotKernel = void (*)(i64*, const int*, u32, u32, u32, u32, u32, u32, u32,
                               u32, u32);
-constexpr RowDotKernel kRowDotKernels[kNumKinds] = {
+constexpr RowDotKernel kRowDotKernels[kNumFormats] = {
     row_dot_kernel<kBf16>, row_dot_kernel<kFp8>, row_dot_kernel<kFp4>};
 
 // Fill (check = false) or compare with the generator (check = true, counted
@@ -478,9 +421,10 @@ void launch_operand(int kind, bool check, void* p, u32 rows, u32 K, u32 operand,
   const u32 vecs_per_row = K * kElemBits[kind] / 128;
   const u64 nvec = (u64)rows * vecs_per_row;
   const unsigned grid = (unsigned)std::min<u64>((nvec + kThreads - 1) / kThreads, 4096);
+  const SeedHalves sd = split_seed(seed);
   hipLaunchKernelGGL(kOperandKernels[kind][check ? 1 : 0], dim3(grid),
                      dim3(kThreads), 0, s, static_cast<u32x4*>(p), nvec,
-                     vecs_per_row, operand, (u32)seed, (u32)(seed >> 32), range, rep);
+                     vecs_per_row, operand, sd.lo, sd.hi, range, rep);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -488,16 +432,16 @@ void launch_operand(int kind, bool check, void* p, u32 rows, u32 K, u32 operand,
 void launch_expected(int kind, u32 M, u32 N, u32 K, u64 seed, u32 range, int* SA,
                      int* SB, i64* R, i64* Q, hipStream_t s) {
   const u32 tm = M / kTile, tn = N / kTile;
-  const u32 lo = (u32)seed, hi = (u32)(seed >> 32);
+  const SeedHalves sd = split_seed(seed);
   auto blocks = [](u64 n) { return dim3((unsigned)((n + kThreads - 1) / kThreads)); };
   hipLaunchKernelGGL(kTileSumKernels[kind], blocks((u64)tm * K), dim3(kThreads), 0,
-                     s, SA, tm, K, 0u, lo, hi, range);
+                     s, SA, tm, K, 0u, sd.lo, sd.hi, range);
   hipLaunchKernelGGL(kTileSumKernels[kind], blocks((u64)tn * K), dim3(kThreads), 0,
-                     s, SB, tn, K, 1u, lo, hi, range);
+                     s, SB, tn, K, 1u, sd.lo, sd.hi, range);
   hipLaunchKernelGGL(kRowDotKernels[kind], dim3(M / kWaves), dim3(kThreads), 0, s, R,
-                     SB, M, tn, K, 0u, lo, hi, range, tn * kTile, (u32)kTile);
+                     SB, M, tn, K, 0u, sd.lo, sd.hi, range, tn * kTile, (u32)kTile);
   hipLaunchKernelGGL(kRowDotKernels[kind], dim3(N / kWaves), dim3(kThreads), 0, s, Q,
-                     SA, N, tm, K, 1u, lo, hi, range, (u32)kTile, tn * kTile);
+                     SA, N, tm, K, 1u, sd.lo, sd.hi, range, (u32)kTile, tn * kTile);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -637,12 +581,12 @@ py::dict gemm_check_verify(const std::string& kind_name, torch::Tensor C, i64 K,
 py::dict gemm_check_geometry() {
   py::dict d, index, min_k, code, inv;
   py::list kinds, loops;
-  for (int i = 0; i < kNumKinds; ++i) {
-    kinds.append(std::string(kKindNames[i]));
-    index[kKindNames[i]] = i;
-    min_k[kKindNames[i]] = kMinK[i];
-    code[kKindNames[i]] = kDefaultCode[i];
-    inv[kKindNames[i]] = (int)kInvGranule[i];
+  for (int i = 0; i < kNumFormats; ++i) {
+    kinds.append(std::string(kFormatNames[i]));
+    index[kFormatNames[i]] = i;
+    min_k[kFormatNames[i]] = kMinK[i];
+    code[kFormatNames[i]] = kDefaultCode[i];
+    inv[kFormatNames[i]] = (int)kInvGranule[i];
   }
   for (int i = 0; i < kNumLoops; ++i) loops.append(std::string(kLoopNames[i]));
   d["kinds"] = kinds;
@@ -797,9 +741,7 @@ py::dict gemm_check(int device, const std::string& kind_name, int size, int iter
                     const std::string& loop_name) {
   const int kind = parse_kind(kind_name);
   const int loop = parse_loop(loop_name);
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  TORCH_CHECK(device >= 0 && device < ndev, "no such device ", device);
+  check_device(device);
   check_extent(size, "size");
   check_k(kind, size);
   check_range(kind, size, range);

@@ -31,13 +31,17 @@
 // a trailing odd word are handled word by word in the same launch. Every
 // index and byte offset is 64-bit.
 //
-// Included by hipcore.hip (needs the torch headers, and hip_host.h for
-// HIP_CHECK and the resource owners the driver holds).
+// fmix32 and the word patterns themselves (pattern_word, pattern_pair) are in
+// burnin_core.h, where burnin_selftest.cpp runs them on the CPU.
+//
+// Included by hipcore.hip (needs the torch headers and hipcore.hip's
+// using-declarations of hip_host.h's resource owners).
+#include "burnin_core.h"
+#include "burnin_host.h"
 
 namespace hbm_memtest {
 
-using u32 = unsigned int;
-using u64 = unsigned long long;
+using namespace burnin;
 
 constexpr int kBlock = 256;
 constexpr int kUnroll = 4;                    // 16-B vectors per lane per tile
@@ -46,88 +50,18 @@ constexpr int kMaxGrid = 2048;
 constexpr u64 kTileVecs = (u64)kBlock * kUnroll;
 
 enum Mode { kWrite = 0, kVerify = 1, kVerifyFlip = 2 };
-enum Pattern { kAddr = 0, kRand = 1, kZero = 2 };
 
 // Device-side report, all u64: [0] mismatching words, [1] OR of
 // expected^actual, [2] record slots claimed, then cap records {g, expected,
 // actual}.
-constexpr int kRepErrors = 0, kRepBits = 1, kRepClaimed = 2, kRepHeader = 3;
-constexpr u64 kMaxRecordsLimit = 65536;
+constexpr int kRepErrors = 0, kRepBits = 1, kRepClaimed = 2, kRepHeader = 3,
+              kRecWords = 3;
 
-__device__ inline u32 fmix32(u32 h) {
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-
-// The two b-dependent terms of "rand". b is the upper half of g ^ seed and
-// changes once per 2^32 words, so a tile that does not straddle a multiple
-// of 2^32 computes them once, wave-uniformly: two of the six multiplies per
-// word leave the per-lane work.
-struct HiTerms {
-  u32 p, q;
-  bool uniform;  // p, q hold for every word of the tile
-  __device__ inline void set(u32 b) {
-    p = b * 0x9E3779B9u;
-    q = b * 0x85EBCA77u + 0x27D4EB2Fu;
-  }
-};
-
-__device__ inline u64 rand_word(u32 a, u32 p, u32 q) {
-  u32 lo = fmix32(a + p);
-  u32 hi = fmix32(~a + q);
-  return ((u64)hi << 32) | lo;
-}
-
-// Expected value of the single word g.
-template <int PAT>
-__device__ inline u64 pattern_word(u64 g, u64 seed, u64 inv) {
-  if (PAT == kZero) return inv;
-  u64 x = g ^ seed;
-  if (PAT == kAddr) return x ^ inv;
-  HiTerms t;
-  t.set((u32)(x >> 32));
-  return rand_word((u32)x, t.p, t.q) ^ inv;
-}
-
-// Terms for the words [g_first, g_first + nwords); every argument is
-// wave-uniform, so the branch on .uniform is a scalar one.
-__device__ inline HiTerms tile_terms(u64 g_first, u64 nwords, u64 seed) {
-  HiTerms t;
-  t.uniform = (g_first >> 32) == ((g_first + (nwords - 1)) >> 32);
-  t.set((u32)((g_first ^ seed) >> 32));
-  return t;
-}
-
-// Expected values of the two words g0, g0 + 1 of one 16-byte vector.
-template <int PAT>
-__device__ inline void pattern_pair(u64 g0, u64 seed, u64 inv,
-                                    const HiTerms& t, u64& w0, u64& w1) {
-  if (PAT == kRand && t.uniform) {
-    const u32 sl = (u32)seed, l0 = (u32)g0;
-    w0 = rand_word(l0 ^ sl, t.p, t.q) ^ inv;
-    w1 = rand_word((l0 + 1u) ^ sl, t.p, t.q) ^ inv;
-  } else {
-    w0 = pattern_word<PAT>(g0, seed, inv);
-    w1 = pattern_word<PAT>(g0 + 1, seed, inv);
-  }
-}
-
-// Mismatch slow path: one claim atomic per bad word, and only while the
-// claim counter is still below the cap, so a badly broken card stops
-// issuing them once the records are full.
+// Mismatch slow path: one claimed record per bad word while slots are left.
 __device__ __noinline__ void record_mismatch(u64* rep, u64 cap, u64 g,
                                              u64 expected, u64 actual) {
-  if (cap == 0) return;
-  u64 claimed = __hip_atomic_load(&rep[kRepClaimed], __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_AGENT);
-  if (claimed >= cap) return;
-  u64 slot = atomicAdd(&rep[kRepClaimed], 1ull);
-  if (slot >= cap) return;
-  u64* r = rep + kRepHeader + 3 * slot;
+  u64* r;
+  if (!claim_record<kRepClaimed, kRepHeader, kRecWords>(rep, cap, r)) return;
   r[0] = g;
   r[1] = expected;
   r[2] = actual;
@@ -288,12 +222,6 @@ int parse_pattern(const std::string& name) {
   return -1;
 }
 
-u64 check_max_records(long long max_records) {
-  TORCH_CHECK(max_records >= 0 && (u64)max_records <= kMaxRecordsLimit,
-              "max_records must be in [0, ", kMaxRecordsLimit, "]");
-  return (u64)max_records;
-}
-
 // ---------------------------------------------------------------------------
 // Tensor bindings: the numerics-testable surface
 // ---------------------------------------------------------------------------
@@ -325,7 +253,7 @@ py::dict report_dict(const u64* h, u64 cap) {
   py::list recs;
   u64 nrec = std::min<u64>(h[kRepClaimed], cap);
   for (u64 i = 0; i < nrec; ++i) {
-    const u64* r = h + kRepHeader + 3 * i;
+    const u64* r = h + kRepHeader + kRecWords * i;
     recs.append(py::make_tuple(py::int_(r[0]), py::int_(r[1]), py::int_(r[2])));
   }
   d["records"] = recs;
@@ -338,7 +266,7 @@ py::dict verify_tensor(int mode, torch::Tensor t, const std::string& pattern,
   check_tensor(t);
   int pat = parse_pattern(pattern);
   u64 cap = check_max_records(max_records);
-  auto rep = torch::zeros({(int64_t)(kRepHeader + 3 * cap)}, t.options());
+  auto rep = torch::zeros({(int64_t)(kRepHeader + kRecWords * cap)}, t.options());
   auto stream = at::hip::getCurrentHIPStream();
   launch(mode, pat, reinterpret_cast<u64*>(t.data_ptr<int64_t>()),
          (u64)t.numel(), base_word, seed, invert,
@@ -436,7 +364,7 @@ DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
   DeviceScope scope(device);
   std::vector<DeviceBuf<u64>> chunks;
   for (u64 w : chunk_words) chunks.emplace_back(device, w);
-  const size_t rep_words = kRepHeader + 3 * cap;
+  const size_t rep_words = kRepHeader + kRecWords * cap;
   DeviceBuf<u64> rep(device, rep_words);
   std::vector<u64> host_rep(rep_words);
 
@@ -487,7 +415,7 @@ DriverResult run_driver(int device, const std::vector<u64>& chunk_words,
     out.bad_bits |= host_rep[kRepBits];
     u64 nrec = std::min<u64>(host_rep[kRepClaimed], cap);
     for (u64 i = 0; i < nrec && out.records.size() < cap; ++i) {
-      const u64* r = host_rep.data() + kRepHeader + 3 * i;
+      const u64* r = host_rep.data() + kRepHeader + kRecWords * i;
       out.records.push_back({name, r[0], r[1], r[2]});
     }
   };
@@ -515,9 +443,7 @@ py::dict hbm_memtest(int device, std::vector<u64> chunk_bytes, u64 seed,
                      const py::sequence& inject_entries, u64 base_word) {
   u64 cap = check_max_records(max_records);
   const std::vector<Inject> inject = parse_inject(inject_entries);
-  int ndev = 0;
-  HIP_CHECK(hipGetDeviceCount(&ndev));
-  TORCH_CHECK(device >= 0 && device < ndev, "no such device ", device);
+  check_device(device);
   TORCH_CHECK(!chunk_bytes.empty(), "chunk_bytes must not be empty");
   std::vector<u64> words;
   for (u64 b : chunk_bytes) {

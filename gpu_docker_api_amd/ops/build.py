@@ -40,6 +40,8 @@ def build_hipcore(force: bool = False) -> str:
     src = os.path.join(CSRC, "hipcore.hip")
     includes = [
         os.path.join(CSRC, "hip_host.h"),
+        os.path.join(CSRC, "burnin_core.h"),
+        os.path.join(CSRC, "burnin_host.h"),
         os.path.join(CSRC, "gemm_bf16.hip"),
         os.path.join(CSRC, "gemm_8phase_common.h"),
         os.path.join(CSRC, "gemm_bf16_8phase.hip"),
