@@ -550,8 +550,44 @@ std::pair<torch::Tensor, torch::Tensor> gemm_check_expected(
   return expected_tensors(parse_kind(kind_name), M, N, K, seed, range);
 }
 
+// The operand check of the driver's read-back on a stored operand: the number
+// of elements of t that differ from the generator's. For the tests; every
+// argument is checked before the launch.
+u64 gemm_check_operand(const std::string& kind_name, int operand, torch::Tensor t,
+                       i64 K, u64 seed, i64 range) {
+  const int kind = parse_kind(kind_name);
+  TORCH_CHECK(operand == 0 || operand == 1, "gemm_check: operand is 0 (A) or 1 (Bt)");
+  check_range(kind, K, range);
+  TORCH_CHECK(K * kElemBits[kind] % 128 == 0,
+              "gemm_check: a row must be a multiple of 16 bytes");
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.is_contiguous() &&
+                  t.scalar_type() == (kind == kBf16 ? torch::kBFloat16 : torch::kUInt8),
+              "gemm_check: the operand must be a contiguous 2-D GPU tensor, bfloat16 "
+              "for bf16 and uint8 for fp8 and fp4");
+  const i64 rows = t.size(0);
+  TORCH_CHECK(rows >= 1 && rows <= kMaxExtent, "gemm_check: rows must be in [1, ",
+              kMaxExtent, "]");
+  TORCH_CHECK(t.size(1) == (kind == kFp4 ? K / 2 : K), "gemm_check: the operand must be "
+              "[rows][K] (fp4: [rows][K/2]) but a row has ", t.size(1), " entries");
+  int cur = -1;
+  HIP_CHECK(hipGetDevice(&cur));
+  TORCH_CHECK(t.get_device() == cur, "gemm_check: the operand is on device ",
+              t.get_device(), " but the current device is ", cur);
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0,
+              "gemm_check: the operand must be 16-byte aligned");
+  auto rep = torch::zeros({(int64_t)kRepHeader},
+                          torch::TensorOptions().device(torch::kCUDA).dtype(torch::kInt64));
+  launch_operand(kind, true, t.data_ptr(), (u32)rows, (u32)K, (u32)operand, seed,
+                 (u32)range, reinterpret_cast<u64*>(rep.data_ptr<int64_t>()),
+                 at::hip::getCurrentHIPStream().stream());
+  auto host = rep.cpu();  // synchronises with the current stream
+  return reinterpret_cast<const u64*>(host.data_ptr<int64_t>())[kRepOperand];
+}
+
+// atomic: the column sums are combined in a tiles * 256 u64 accumulator, as
+// the serial-atomic and verify-atomic loops of the driver do.
 py::dict gemm_check_verify(const std::string& kind_name, torch::Tensor C, i64 K,
-                           u64 seed, i64 range, i64 max_records) {
+                           u64 seed, i64 range, i64 max_records, bool atomic) {
   const int kind = parse_kind(kind_name);
   TORCH_CHECK(C.is_cuda() && C.scalar_type() == torch::kFloat32 && C.dim() == 2 &&
                   C.is_contiguous(),
@@ -569,11 +605,15 @@ py::dict gemm_check_verify(const std::string& kind_name, torch::Tensor C, i64 K,
   auto slab = torch::empty({(M / kTile) * (N / kTile) * kStrips * kTile},
                            opts.dtype(torch::kInt32));
   auto rep = torch::zeros({(int64_t)rep_words(cap)}, opts.dtype(torch::kInt64));
+  torch::Tensor acc;
+  if (atomic)
+    acc = torch::empty({(M / kTile) * (N / kTile) * kTile}, opts.dtype(torch::kInt64));
   launch_verify(kind, C.data_ptr<float>(), (u32)M, (u32)N,
                 reinterpret_cast<const i64*>(rq.first.data_ptr<int64_t>()),
                 reinterpret_cast<const i64*>(rq.second.data_ptr<int64_t>()),
                 slab.data_ptr<int>(), reinterpret_cast<u64*>(rep.data_ptr<int64_t>()),
-                cap, 0, at::hip::getCurrentHIPStream().stream());
+                cap, 0, at::hip::getCurrentHIPStream().stream(),
+                atomic ? reinterpret_cast<u64*>(acc.data_ptr<int64_t>()) : nullptr);
   auto host = rep.cpu();  // synchronises with the current stream
   return report_dict(reinterpret_cast<const u64*>(host.data_ptr<int64_t>()), cap);
 }

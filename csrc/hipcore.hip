@@ -898,6 +898,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("seed"), py::arg("range"));
   m.def("gemm_check_verify", &gemm_check::gemm_check_verify, py::arg("kind"),
         py::arg("C"), py::arg("K"), py::arg("seed"), py::arg("range"),
-        py::arg("max_records") = 32);
+        py::arg("max_records") = 32, py::arg("atomic") = false);
+  m.def("gemm_check_operand", &gemm_check::gemm_check_operand, py::arg("kind"),
+        py::arg("operand"), py::arg("t"), py::arg("K"), py::arg("seed"),
+        py::arg("range"));
   m.def("gemm_check_geometry", &gemm_check::gemm_check_geometry);
 }

@@ -21,6 +21,8 @@ Plain module, not a conftest: it changes nothing about collection.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
 import kernel_refs as kr
@@ -115,6 +117,62 @@ def expected_sums(a: np.ndarray, b: np.ndarray):
     R = (a @ sb.T).reshape(tm, TILE, tn).transpose(0, 2, 1)
     Q = (b @ sa.T).reshape(tn, TILE, tm).transpose(2, 0, 1)
     return np.ascontiguousarray(R), np.ascontiguousarray(Q)
+
+
+class VerifyClass(NamedTuple):
+    """Who looks at element (row, col) of a 256 x 256 tile: the workgroup of
+    `strip` (64 rows), in it `wave` (16 rows), whose lane `j` reports the row
+    and whose `lane` loads the element as float `e` of its 16-byte vector."""
+    strip: int
+    wave: int
+    j: int
+    lane: int
+    e: int
+
+    @property
+    def c(self) -> int:
+        """The thread of the column check that compares this column."""
+        return 4 * self.lane + self.e
+
+
+def verify_class(row: int, col: int) -> VerifyClass:
+    """The verifier's share of an in-tile position, from the verify section
+    of the kernel file's header: a workgroup takes a strip of 64 rows, wave w
+    of it the rows 16w..16w+15, and 64 lanes x float4 are one tile row."""
+    if not (0 <= row < TILE and 0 <= col < TILE):
+        raise ValueError(f"({row}, {col}) is outside a tile")
+    return VerifyClass(row // 64, (row % 64) // 16, row % 16, col // 4, col % 4)
+
+
+def operand_diff_count(kind: str, stored_a: np.ndarray, stored_b: np.ndarray) -> int:
+    """Number of elements in which two stored operands differ: bf16 words,
+    e4m3 bytes, e2m1 nibbles (two to the byte)."""
+    if stored_a.shape != stored_b.shape or stored_a.dtype != stored_b.dtype:
+        raise ValueError("operands of different shape or type")
+    if kind != "fp4":
+        return int(np.count_nonzero(stored_a != stored_b))
+    d = stored_a.astype(np.uint8) ^ stored_b.astype(np.uint8)
+    return int(np.count_nonzero(d & 0x0F) + np.count_nonzero(d & 0xF0))
+
+
+def legal_other_code(kind: str, code: int, rng: int) -> int:
+    """A different code of the same element set, so that an operand with it
+    in place still has exact sums: bf16 (bit pattern) the neighbouring
+    numerator in [-r, r], e4m3 the next code of e4m3_codes_of_range (the last
+    wraps to zero), e2m1 the code with the other mantissa bit."""
+    code = int(code)
+    if kind == "bf16":
+        m = float(kr.bf16_bits_to_f64(np.array([code], dtype=np.uint16))[0]) * 16.0
+        if m != int(m) or abs(m) > rng:
+            raise ValueError(f"bf16 {code:#06x} is not in the set of range {rng}")
+        other = int(m) + 1 if m < rng else int(m) - 1
+        return int(kr.f32_to_bf16_bits(np.array([other / 16.0], dtype=np.float32))[0])
+    if kind == "fp8":
+        legal = e4m3_codes_of_range(rng).tolist()
+        return legal[(legal.index(code) + 1) % len(legal)]
+    if not 0 <= code < 16:
+        raise ValueError(f"{code} is no e2m1 code")
+    return code ^ 1
 
 
 def classify(C: np.ndarray, inv_granule: float, R: np.ndarray, Q: np.ndarray) -> dict:

@@ -107,6 +107,72 @@ def test_expected_sums_are_the_checksums_of_the_product():
 
 
 # ---------------------------------------------------------------------------
+# helpers of the verifier and operand-check tests
+# ---------------------------------------------------------------------------
+
+def test_verify_class_is_a_bijection_with_three_values_by_hand():
+    # row 150 = 2 * 64 + 22 = 2 * 64 + 1 * 16 + 6; col 77 = 19 * 4 + 1
+    assert tuple(gr.verify_class(150, 77)) == (2, 1, 6, 19, 1)
+    assert tuple(gr.verify_class(0, 0)) == (0, 0, 0, 0, 0)
+    assert tuple(gr.verify_class(255, 255)) == (3, 3, 15, 63, 3)
+    seen = set()
+    for row in range(256):
+        for col in range(256):
+            k = gr.verify_class(row, col)
+            assert 0 <= k.strip < 4 and 0 <= k.wave < 4 and 0 <= k.j < 16
+            assert 0 <= k.lane < 64 and 0 <= k.e < 4
+            assert k.c == col and 64 * k.strip + 16 * k.wave + k.j == row
+            seen.add(tuple(k))
+    assert len(seen) == 4 * 4 * 16 * 64 * 4 == 256 * 256
+    for bad in ((256, 0), (0, 256), (-1, 0)):
+        with pytest.raises(ValueError):
+            gr.verify_class(*bad)
+
+
+def test_operand_diff_count_counts_elements():
+    a = np.zeros((2, 8), dtype=np.uint8)
+    b = a.copy()
+    b[1, 3] = 0x21  # one byte, both nibbles changed
+    assert gr.operand_diff_count("fp4", a, b) == 2
+    assert gr.operand_diff_count("fp8", a, b) == 1
+    b[0, 0] = 0x30  # a high nibble alone, then a low nibble alone
+    b[0, 7] = 0x03
+    assert gr.operand_diff_count("fp4", a, b) == 4
+    assert gr.operand_diff_count("fp8", a, b) == 3
+    assert gr.operand_diff_count("fp4", a, a) == gr.operand_diff_count("fp8", a, a) == 0
+    w = np.zeros((2, 8), dtype=np.int16)
+    v = w.copy()
+    v[0, 1] = -32768  # the sign bit alone
+    v[1, 7] = 0x0101  # both bytes of one word
+    assert gr.operand_diff_count("bf16", w, v) == 2
+    with pytest.raises(ValueError):
+        gr.operand_diff_count("fp8", a, a[:1])
+
+
+@pytest.mark.parametrize("kind,rng", [("bf16", 127), ("bf16", 90), ("bf16", 1), ("fp8", 4),
+                                      ("fp8", 3), ("fp8", 1), ("fp4", 16)])
+def test_legal_other_code_stays_in_the_set_and_differs(kind, rng):
+    if kind == "bf16":
+        legal = kr.f32_to_bf16_bits(
+            (np.arange(-rng, rng + 1) / 16.0).astype(np.float32)).tolist()
+    elif kind == "fp8":
+        legal = gr.e4m3_codes_of_range(rng).tolist()
+    else:
+        legal = list(range(16))
+    others = [gr.legal_other_code(kind, c, rng) for c in legal]
+    assert all(o in legal for o in others)
+    assert all(o != c for o, c in zip(others, legal))
+    # and in value, so that a sum through it moves (e2m1 +0 and -0 aside,
+    # which the other mantissa bit never maps onto each other)
+    code_t = np.uint16 if kind == "bf16" else np.uint8
+    assert np.all(gr.decode(kind, np.array(others, dtype=code_t))
+                  != gr.decode(kind, np.array(legal, dtype=code_t)))
+    if kind == "bf16":
+        with pytest.raises(ValueError):
+            gr.legal_other_code(kind, 0x3F81, rng)  # 1 + 2^-7: no sixteenth
+
+
+# ---------------------------------------------------------------------------
 # owner map
 # ---------------------------------------------------------------------------
 
