@@ -13,7 +13,11 @@
 //   * the exactness condition accepts the largest K with top^2 * K <= 2^24 at
 //     each format's full range and rejects K + 1;
 //   * pattern_pair with tile_terms equals two pattern_word calls for tiles
-//     that cross no multiple of 2^32, that cross one and that start on one.
+//     that cross no multiple of 2^32, that cross one and that start on one;
+//   * the VALU section: the exponent windows, fp16 rounding at ties, at the
+//     subnormal boundary and at the largest finite value, the condition
+//     under which the packed-fp16 twin is exact in double, the twins of the
+//     device builtins, and that a multiply and an add stayed two roundings.
 //
 // With a sub-command it prints raw values, one number per token, for
 // tests/test_burnin_core_cpu.py to compare with the numpy references:
@@ -22,8 +26,10 @@
 //   gemm <kind> <operand> <rows> <K> <seed> <range>   codes, then numerators, [rows][K]
 //   mem <pattern> <seed> <base_word> <n> <invert>     n words
 //   exact <kind> <range> <K>                          1 if the sums are exact, else 0
+//   valu <test> <round> <seed>                        steps*64 result bits, then 64 digests
 //
-// fmt and kind are bf16, fp8 or fp4; pattern is addr, rand or zero. The tag
+// fmt and kind are bf16, fp8 or fp4; pattern is addr, rand or zero; test is
+// int, f32, f64 or pk16 (trans has no host twin). The tag
 // layouts and cu_check's K are the checks' own definitions (cu_check.hip,
 // gemm_check.hip) and are written out again here.
 #include <cmath>
@@ -166,9 +172,113 @@ static void check_patterns() {
   }
 }
 
+// The VALU section: window constants, fp16 rounding where it can go wrong,
+// the double-exactness condition and the host twins of the device builtins.
+static void check_valu() {
+  // windows: every operand normal, magnitudes in [2^-7, 2^8) / [2^-4, 2^5)
+  CHECK(kValuF32ExpLo == 120 && kValuF32ExpHi == 134);
+  CHECK(kValuF64ExpLo == 1016 && kValuF64ExpHi == 1030);
+  CHECK(kValuF16ExpLo == 11 && kValuF16ExpHi == 19);
+  CHECK(kValuSteps == 256 && kNumValuExact + 1 == kNumValuTests);
+  u32 f32_fields = 0, f64_fields = 0, f16_fields = 0;
+  for (u32 i = 0; i < 4096; ++i) {
+    const u32 u = fmix32(i), v = fmix32(~i);
+    const float f = valu_f32(u);
+    const u32 fb = __builtin_bit_cast(u32, f), fe = (fb >> 23) & 0xFFu;
+    CHECK(fe >= kValuF32ExpLo && fe <= kValuF32ExpHi && ((fb ^ u) & 0x807FFFFFu) == 0);
+    CHECK(std::fabs(f) >= std::ldexp(1.0, -7) && std::fabs(f) < std::ldexp(1.0, 8));
+    f32_fields |= 1u << (fe - kValuF32ExpLo);
+    const double d = valu_f64(u, v);
+    const u64 db = __builtin_bit_cast(u64, d);
+    const u32 de = (u32)(db >> 52) & 0x7FFu;
+    CHECK(de >= kValuF64ExpLo && de <= kValuF64ExpHi && (u32)db == v);
+    CHECK(((u32)(db >> 32) ^ u) << 12 == 0 && (db >> 63) == (u >> 31));
+    f64_fields |= 1u << (de - kValuF64ExpLo);
+    const u32 h = valu_f16(u), he = (h >> 10) & 31u;
+    CHECK(h < 0x10000u && he >= kValuF16ExpLo && he <= kValuF16ExpHi);
+    CHECK(((h ^ u) & 0x83FFu) == 0);
+    f16_fields |= 1u << (he - kValuF16ExpLo);
+    CHECK(valu_pk16(u) == (valu_f16(u & 0xFFFFu) | valu_f16(u >> 16) << 16));
+  }
+  CHECK(f32_fields == 0x7FFFu && f64_fields == 0x7FFFu && f16_fields == 0x1FFu);
+
+  // the double twin is exact: bits 2^-28 .. 2^10 at this window, 39 of them,
+  // and 53 is the limit
+  CHECK(valu_pk16_span_bits(kValuF16ExpLo, kValuF16ExpHi) == 39);
+  CHECK(valu_pk16_double_exact(kValuF16ExpLo, kValuF16ExpHi));
+  CHECK(valu_pk16_double_exact(4, 19) && !valu_pk16_double_exact(3, 19));
+
+  // fp16 decode and round trip of every finite code
+  for (u32 h = 0; h < 0x10000u; ++h) {
+    if (((h >> 10) & 31u) == 31u) continue;
+    const u32 e = (h >> 10) & 31u, m = h & 0x3FFu;
+    const double mag = e == 0 ? std::ldexp(m / 1024.0, -14) : std::ldexp(1.0 + m / 1024.0, (int)e - 15);
+    CHECK(f16_bits_to_double(h) == ((h & 0x8000u) ? -mag : mag));
+    CHECK(f16_bits_from_double(f16_bits_to_double(h)) == h);
+  }
+  // ties to even, and just beside the tie
+  CHECK(f16_bits_from_double(1.0 + std::ldexp(1.0, -11)) == 0x3C00u);  // tie, even below
+  CHECK(f16_bits_from_double(1.0 + std::ldexp(3.0, -11)) == 0x3C02u);  // tie, even above
+  CHECK(f16_bits_from_double(1.0 + std::ldexp(1.0, -11) + std::ldexp(1.0, -40)) == 0x3C01u);
+  CHECK(f16_bits_from_double(1.0 + std::ldexp(1.0, -11) - std::ldexp(1.0, -40)) == 0x3C00u);
+  CHECK(f16_bits_from_double(-(1.0 + std::ldexp(3.0, -11))) == 0xBC02u);
+  // the subnormal boundary
+  CHECK(f16_bits_from_double(std::ldexp(1.0, -14)) == 0x0400u);   // smallest normal
+  CHECK(f16_bits_from_double(std::ldexp(1023.0, -24)) == 0x03FFu);  // largest subnormal
+  CHECK(f16_bits_from_double(std::ldexp(1023.5, -24)) == 0x0400u);  // tie up to normal
+  CHECK(f16_bits_from_double(std::ldexp(1022.5, -24)) == 0x03FEu);  // tie to even
+  CHECK(f16_bits_from_double(std::ldexp(1.0, -24)) == 0x0001u);   // smallest subnormal
+  CHECK(f16_bits_from_double(std::ldexp(1.0, -25)) == 0x0000u);   // tie to zero
+  CHECK(f16_bits_from_double(std::ldexp(1.0, -25) + std::ldexp(1.0, -60)) == 0x0001u);
+  CHECK(f16_bits_from_double(std::ldexp(1.5, -24)) == 0x0002u);   // tie to even
+  CHECK(f16_bits_from_double(-std::ldexp(1.0, -28)) == 0x8000u);  // the lowest product bit
+  CHECK(f16_bits_from_double(0.0) == 0x0000u && f16_bits_from_double(-0.0) == 0x8000u);
+  // the largest finite value
+  CHECK(f16_bits_from_double(65504.0) == 0x7BFFu);
+  CHECK(f16_bits_from_double(65519.99) == 0x7BFFu);
+  CHECK(f16_bits_from_double(65520.0) == 0x7C00u);  // tie: even is 2^16
+  CHECK(f16_bits_from_double(-1e30) == 0xFC00u);
+  // a cancelling fma lands in the subnormal range: 1.5*1.5 - 2.25 = 0, and
+  // (1 + 2^-10) * (1/16 + 2^-14) - (1/16 + 2^-13) = 2^-24, the smallest subnormal
+  CHECK(valu_f16_fma_twin(0x3E00u, 0x3E00u, 0xC080u) == 0x0000u);
+  CHECK(valu_f16_fma_twin(0x3C01u, 0x2C01u, 0xAC02u) == 0x0001u);
+
+  // the twins of the device builtins, by hand
+  CHECK(valu_perm_twin(0xAABBCCDDu, 0x11223344u, 0x00010203u) == 0x44332211u);
+  CHECK(valu_perm_twin(0xAABBCCDDu, 0x11223344u, 0x07060504u) == 0xAABBCCDDu);
+  CHECK(valu_perm_twin(0xAABBCCDDu, 0x11223344u, 0x04000703u) == 0xDD44AA11u);
+  CHECK(valu_sad_u8_twin(0x01FF0010u, 0xFF0100F0u, 5u) == 5u + 254u + 254u + 0u + 224u);
+  CHECK(valu_sad_u8_twin(0u, 0xFFFFFFFFu, 0xFFFFFFFFu) == 4u * 255u - 1u);
+  CHECK(valu_bfe_twin(0xDEADBEEFu, 8, 12) == 0xDBEu && valu_bfe_twin(0xDEADBEEFu, 28, 8) == 0xDu);
+  CHECK(valu_bfe_twin(0xDEADBEEFu, 0, 0) == 0u && valu_bfe_twin(0xDEADBEEFu, 31, 31) == 1u);
+
+  // a separate multiply and add stayed two roundings in this build: with
+  // a = b = 1 + 2^-12 the product's 2^-24 is lost before the add, kept by fma
+  {
+    volatile float a = 1.0f + std::ldexp(1.0f, -12), c = -1.0f;
+    const float p = a * a, two = p + c, one = __builtin_fmaf(a, a, c);
+    CHECK(two == std::ldexp(1.0f, -11) && one == std::ldexp(1.0f, -11) + std::ldexp(1.0f, -24));
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Sub-commands
 // ---------------------------------------------------------------------------
+
+// valu: the steps*64 result bits of one (test, round), [step][lane], a 64-bit
+// result as hi << 32 | lo; then the 64 digests.
+template <int TEST>
+static void print_valu(u32 round, u64 seed) {
+  const SeedHalves s = split_seed(seed);
+  const u32 base = key_base(s.lo, s.hi, round);
+  std::vector<u64> bits((size_t)kValuSteps * 64);
+  for (u32 lane = 0; lane < 64; ++lane)
+    valu_round<TEST>(base, lane, [&](u32 step, const ValuResult& r) {
+      bits[(size_t)step * 64 + lane] = (u64)(r.wide ? r.hi : 0u) << 32 | r.lo;
+    });
+  for (u64 b : bits) std::printf("%llu\n", b);
+  for (u32 lane = 0; lane < 64; ++lane) std::printf("%u\n", valu_digest<TEST>(base, lane));
+}
 
 static int parse_name(const char* s, const char* const* names, int n, const char* what) {
   for (int i = 0; i < n; ++i)
@@ -228,7 +338,8 @@ static int usage() {
                "       burnin_selftest cu <fmt> <tile> <seed> <operand>\n"
                "       burnin_selftest gemm <kind> <operand> <rows> <K> <seed> <range>\n"
                "       burnin_selftest mem <pattern> <seed> <base_word> <n> <invert>\n"
-               "       burnin_selftest exact <kind> <range> <K>\n");
+               "       burnin_selftest exact <kind> <range> <K>\n"
+               "       burnin_selftest valu <test> <round> <seed>\n");
   return 2;
 }
 
@@ -239,6 +350,7 @@ int main(int argc, char** argv) {
     check_codes<kFp4>();
     check_exactness();
     check_patterns();
+    check_valu();
     if (g_failed) {
       std::fprintf(stderr, "burnin selftest: %d check(s) failed\n", g_failed);
       return 1;
@@ -286,6 +398,16 @@ int main(int argc, char** argv) {
     const u64 range = parse_u64(argv[3]), K = parse_u64(argv[4]);
     if (!legal_range(kind, range) || K < 1 || K > (u64)kTwo24) return usage();
     std::printf("%d\n", sums_exact(kind, (i64)range, (i64)K) ? 1 : 0);
+    return 0;
+  }
+  if (cmd == "valu" && argc == 5) {
+    const int test = parse_name(argv[2], kValuTestNames, kNumValuExact, "exact VALU test");
+    const u64 round = parse_u64(argv[3]), seed = parse_u64(argv[4]);
+    if (round >= 4096) return usage();
+    if (test == kValuInt) print_valu<kValuInt>((u32)round, seed);
+    if (test == kValuF32) print_valu<kValuF32>((u32)round, seed);
+    if (test == kValuF64) print_valu<kValuF64>((u32)round, seed);
+    if (test == kValuPk16) print_valu<kValuPk16>((u32)round, seed);
     return 0;
   }
   return usage();

@@ -1,7 +1,7 @@
 // Host-side HIP resource layer of the native core: the one HIP_CHECK and the
 // one owner each for device memory, streams, events and the current device.
 // hipcore.hip and the files it includes (hbm_memtest.hip, cu_check.hip,
-// gemm_check.hip, and burnin_host.h for HIP_CHECK) create and release these
+// valu_check.hip, gemm_check.hip, and burnin_host.h for HIP_CHECK) create and release these
 // resources here and nowhere else, so a throwing HIP_CHECK
 // between an allocation and its release leaks nothing, and every entry point
 // hands the calling thread back on the device it came in on.

@@ -12,6 +12,9 @@
 //   * Per-CU MFMA and LDS check (cu_check.hip): exact tiles in bf16, MX-fp8
 //     and MX-fp4 checked on the CU that computed them, its whole LDS
 //     pattern-tested, every result tagged with the XCC and CU id.
+//   * Per-SIMD vector ALU check (valu_check.hip): integer, fp32, fp64, packed
+//     fp16 and transcendental chains with known digests on every SIMD of
+//     every CU, every result tagged with the XCC, CU and SIMD id.
 //   * Checked GEMM loop (gemm_check.hip): the 256^2 kernels at full size on
 //     exactly-summable operands, every result verified on the device with
 //     integer row and column checksums per tile.
@@ -29,9 +32,11 @@
 #include <hip/hip_bf16.h>
 
 #include <algorithm>
+#include <chrono>
 #include <functional>
 #include <map>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "hip_host.h"
@@ -197,6 +202,7 @@ __global__ void mfma_warmup_kernel(float* __restrict__ sink, int iters) {
 #include "gemm_fp8_mx.hip"
 #include "hbm_memtest.hip"
 #include "cu_check.hip"
+#include "valu_check.hip"
 
 namespace {
 
@@ -886,6 +892,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cu_check_tile", &cu_check::cu_check_tile, py::arg("fmt"),
         py::arg("tile"), py::arg("seed"));
   m.def("cu_check_geometry", &cu_check::cu_check_geometry);
+  m.def("valu_check", &valu_check::valu_check, py::arg("device"), py::arg("rounds"),
+        py::arg("seed"), py::arg("grid_mult") = 2,
+        py::arg("inject") = std::vector<std::vector<long long>>{});
+  m.def("valu_check_values", &valu_check::valu_check_values, py::arg("test"),
+        py::arg("round"), py::arg("seed"));
+  m.def("valu_check_table", &valu_check::valu_check_table, py::arg("rounds"),
+        py::arg("seed"));
+  m.def("valu_check_geometry", &valu_check::valu_check_geometry);
   m.def("gemm_check", &gemm_check::gemm_check, py::arg("device"), py::arg("kind"),
         py::arg("size"), py::arg("iters"), py::arg("seed"), py::arg("range"),
         py::arg("code") = -1, py::arg("max_records") = 32,

@@ -259,10 +259,13 @@ def res_validate(
         "--gemm-check",
         help="also run this many checksum-verified full-size GEMMs per format (0 = off)",
     ),
+    valu_check: int = typer.Option(
+        0, "--valu-check", help="also check every SIMD's vector ALU for this many rounds (0 = off)"
+    ),
 ):
     """Burn-in free GPUs (HBM bandwidth + bf16/MX-fp8/MX-fp4 MFMA TFLOPS,
-    optionally an HBM pattern memory test, a per-CU compute check and a
-    checked GEMM loop)."""
+    optionally an HBM pattern memory test, a per-CU compute check, a
+    checked GEMM loop and a per-SIMD vector ALU check)."""
     body = {"size": size, "iters": iters}
     if memtest_mib:
         body["memtestMiB"] = memtest_mib
@@ -270,6 +273,8 @@ def res_validate(
         body["cuCheck"] = cu_check
     if gemm_check != 0:
         body["gemmCheck"] = gemm_check
+    if valu_check > 0:
+        body["valuCheck"] = valu_check
     with _client() as c:
         _show(
             c.post(

@@ -48,6 +48,7 @@ def build_hipcore(force: bool = False) -> str:
         os.path.join(CSRC, "gemm_fp8_mx.hip"),
         os.path.join(CSRC, "hbm_memtest.hip"),
         os.path.join(CSRC, "cu_check.hip"),
+        os.path.join(CSRC, "valu_check.hip"),
         os.path.join(CSRC, "gemm_check.hip"),
     ]
     out = os.path.join(OPS, "_hipcore.so")

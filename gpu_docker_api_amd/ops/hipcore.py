@@ -240,6 +240,97 @@ def cu_check_gpu(
     return report
 
 
+VALU_CHECK_SEED = 0x7A1C0DE5EED5A1D5
+VALU_CHECK_ROUNDS = 8
+VALU_CHECK_TESTS = ("int", "f32", "f64", "pk16", "trans")
+
+
+def valu_check_fold(records: list, cus_expected: int) -> dict:
+    """Fold the per-workgroup records of valu_check by the SIMD each wave ran
+    on: (cu_check_key, SIMD field of that wave's HW_ID). Pure Python.
+    `bad_simds` lists every SIMD with a mismatch, with its counts per test and
+    the first mismatch one of its waves reported. Coverage (`cus_seen`,
+    `simds_seen`) is reported, never judged. `trans_reference_suspect` is true
+    when more than half of the SIMDs seen report trans mismatches while their
+    exact tests are clean: the one workgroup the trans table came from is then
+    the likelier culprit than half the card."""
+    simds: dict = {}
+    cus = set()
+    split = 0
+    errors = {t: 0 for t in VALU_CHECK_TESTS}
+    for rec in records:
+        key = cu_check_key(rec)
+        cus.add(key)
+        if len({(int(h) >> 8) & 0xFF for h in rec["hw_id"]}) > 1:
+            split += 1  # waves of one workgroup on different "CUs": layout is off
+        for hw, wave in zip(rec["hw_id"], rec["waves"]):
+            simd = simds.setdefault(
+                (key, hw_id_fields(hw)["simd"]),
+                {"tests": {t: 0 for t in VALU_CHECK_TESTS}, "first": None},
+            )
+            for t in VALU_CHECK_TESTS:
+                n = int(wave["counts"].get(t, 0))
+                simd["tests"][t] += n
+                errors[t] += n
+            if simd["first"] is None and wave.get("first") is not None:
+                simd["first"] = dict(wave["first"])
+    bad = []
+    trans_only = 0
+    for (key, s) in sorted(simds):
+        simd = simds[(key, s)]
+        total = sum(simd["tests"].values())
+        if total == 0:
+            continue
+        if simd["tests"]["trans"] == total:
+            trans_only += 1
+        f = hw_id_fields(key << 8)
+        bad.append(
+            {
+                "xcc": key >> 8,
+                "se": f["se"],
+                "sh": f["sh"],
+                "cu": f["cu"],
+                "simd": s,
+                "key": key,
+                "tests": dict(simd["tests"]),
+                "first": simd["first"],
+            }
+        )
+    return {
+        "cus_expected": int(cus_expected),
+        "cus_seen": len(cus),
+        "simds_seen": len(simds),
+        "workgroups": len(records),
+        "split_workgroups": split,
+        "errors": {"total": sum(errors.values()), **errors},
+        "bad_simds": bad,
+        "trans_reference_suspect": 2 * trans_only > len(simds),
+    }
+
+
+def valu_check_gpu(
+    index: int,
+    rounds: int = VALU_CHECK_ROUNDS,
+    seed: int = VALU_CHECK_SEED,
+    inject: Optional[list] = None,
+) -> dict:
+    """Per-SIMD vector ALU check of GPU `index` (csrc/valu_check.hip): every
+    SIMD of every CU runs `rounds` rounds of integer, fp32, fp64, packed-fp16
+    and transcendental chains and compares each lane's digest with a table
+    (computed on the host for the exact tests, taken from a reference launch
+    for trans). Returns the fold by SIMD plus how the pass ran."""
+    ext = load_ext()
+    cus = int(ext.device_info(index)["multiProcessorCount"])
+    raw = ext.valu_check(index, int(rounds), seed, 2, list(inject or []))
+    report = valu_check_fold(raw["records"], cus)
+    report["rounds"] = int(rounds)
+    report["launches"] = raw["launches"]
+    report["seconds"] = round(raw["seconds"], 4)
+    report["table_seconds"] = round(raw["table_seconds"], 4)
+    report["trans_reference"] = dict(raw["trans_reference"])
+    return report
+
+
 GEMM_CHECK_SEED = 0x6E44C4EC5EED0001
 GEMM_CHECK_KINDS = ("bf16", "fp8", "fp4")
 GEMM_CHECK_TILE = 256
@@ -414,6 +505,7 @@ def validate_gpus(
     memtest_mib: int = 0,
     cu_rounds: int = 0,
     gemm_check_iters: int = 0,
+    valu_rounds: int = 0,
 ) -> dict:
     """Per-GPU health burn-in: HBM stream bandwidth + dense bf16 MFMA GEMM
     (the 8-phase 256^2 structure, ~1.1 PF) + the MX-fp8 path (block-scaled
@@ -427,7 +519,9 @@ def validate_gpus(
     CUs the pass did not reach are reported, not judged. With
     gemm_check_iters > 0 each GPU also gets the checked GEMM loop
     (gemm_check_gpu) at `size` and is unhealthy if a single checksum, element
-    or stored operand was wrong in any format."""
+    or stored operand was wrong in any format. With valu_rounds > 0 each GPU
+    also gets the per-SIMD vector ALU check (valu_check_gpu) and is unhealthy
+    if a single lane's digest was wrong."""
     ext = load_ext()
     n = ext.device_count()
     idx = list(indices) if indices else list(range(n))
@@ -454,6 +548,8 @@ def validate_gpus(
             entry["cu_check"] = cu_check_gpu(i, cu_rounds)
         if gemm_check_iters > 0:
             entry["gemm_check"] = gemm_check_gpu(i, size, gemm_check_iters)
+        if valu_rounds > 0:
+            entry["valu_check"] = valu_check_gpu(i, valu_rounds)
         report["gpus"].append(entry)
     vals = [g["bf16_tflops"] for g in report["gpus"]]
     if vals:
@@ -466,6 +562,8 @@ def validate_gpus(
                 g["healthy"] = bool(g["healthy"] and g["cu_check"]["errors"]["total"] == 0)
             if "gemm_check" in g:
                 g["healthy"] = bool(g["healthy"] and g["gemm_check"]["errors_total"] == 0)
+            if "valu_check" in g:
+                g["healthy"] = bool(g["healthy"] and g["valu_check"]["errors"]["total"] == 0)
     return report
 
 
@@ -476,6 +574,7 @@ async def validate_gpus_async(
     memtest_mib: int = 0,
     cu_rounds: int = 0,
     gemm_check_iters: int = 0,
+    valu_rounds: int = 0,
 ) -> dict:
     return await asyncio.get_running_loop().run_in_executor(
         None,
@@ -486,6 +585,7 @@ async def validate_gpus_async(
             memtest_mib=memtest_mib,
             cu_rounds=cu_rounds,
             gemm_check_iters=gemm_check_iters,
+            valu_rounds=valu_rounds,
         ),
     )
 

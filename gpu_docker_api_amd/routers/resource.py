@@ -27,7 +27,8 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
         """MI355X extension: burn-in the node's FREE GPUs (HBM bandwidth +
         dense bf16 MFMA GEMM, with `memtestMiB` an HBM pattern memory test
         with `cuCheck` a per-CU MFMA and LDS check, with `gemmCheck` a
-        checked loop of the full-size GEMMs) before trusting them
+        checked loop of the full-size GEMMs, with `valuCheck` a per-SIMD
+        vector ALU check) before trusting them
         with placements. Busy GPUs are skipped unless explicitly listed."""
         try:
             body = await request.json()
@@ -62,6 +63,9 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
             gemm_check = body.get("gemmCheck", 0)
             if isinstance(gemm_check, bool) or not isinstance(gemm_check, int):
                 raise TypeError("gemmCheck must be an int")
+            valu_rounds = body.get("valuCheck", 0)
+            if isinstance(valu_rounds, bool) or not isinstance(valu_rounds, int):
+                raise TypeError("valuCheck must be an int")
         except (TypeError, ValueError):
             from .codes import Code
             from .response import error
@@ -80,6 +84,9 @@ def make_router(gpu: GpuScheduler, cpu: CpuScheduler, ports: PortScheduler) -> A
             # checked GEMM loop: off at 0, else 1 .. 100000 iterations a format
             if gemm_check != 0:
                 extra["gemm_check_iters"] = max(1, min(gemm_check, 100000))
+            # per-SIMD vector ALU check: off at 0, else 1 .. 4096 rounds
+            if valu_rounds != 0:
+                extra["valu_rounds"] = max(1, min(valu_rounds, 4096))
             report = await hipcore.validate_gpus_async(
                 idx,
                 max(256, min(size, 16384)),
